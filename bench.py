@@ -1,9 +1,14 @@
 #!/usr/bin/env python
 """Benchmark of the Monkey-Net frame-generation hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
-    (N > 1 without RANK in the environment: re-executes itself under `python -m torch.distributed.run --nnodes=1
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+    (N > 1 without RANK in the environment: runs itself as a child `python -m torch.distributed.run --nnodes=1
      --nproc-per-node N --master-addr 127.0.0.1`, one rank per GPU over RCCL; the driver's own launch is left alone)
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, ...); the
+records below other than the headline are measured only with --full.  --dump-outputs DIR writes what the last timed
+step returned (the losses and the generated tensors; inputs and weights are seeded, so two builds can be compared
+output for output).
 
 A "step" is one full training iteration of train.py:110-136 on one synthetic batch: KPDetector (source + driving
 frame) -> generator -> discriminator on (generated, real) -> losses -> backward -> Adam (generator, kp detector),
@@ -106,7 +111,20 @@ def parse():
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="CPU check of the N-rank self-launch: every rank joins a gloo group, rank 0 prints one line")
     ap.add_argument("--print-launch", action="store_true", help="print the N-rank launch command and exit")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: per-kernel profile and rooflines, hot_path_only, the dropin "
+                         "loops, the taichi / vox / bair / bf16x3 legs, the CPU baseline and its recon L1 (their own flags "
+                         "still switch each off).  Without it a run only sets up, warms up, times K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (losses, generated tensors) as DIR/<name>.npy, float32 / "
+                         "float64, at most 64 MB in all")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        args.no_profile, args.no_cpu_baseline = True, True
+        args.dropin, args.taichi_leg, args.extra_legs = 0, 0, 0
+    return args
 
 
 def _free_port():
@@ -139,7 +157,9 @@ def self_launch(args):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # dmabuf IPC: RCCL needs it on this driver
     env.setdefault("OMP_NUM_THREADS", "4")
     sys.stdout.flush()
-    os.execve(sys.executable, cmd, env)
+    # the ranks are child processes: this one has already opened the HIP runtime (device_count) and is not replaced
+    import subprocess
+    sys.exit(subprocess.call(cmd, env=env))
 
 
 def launcher_selftest():
@@ -715,6 +735,47 @@ def emit(obj):
         os.write(_JSON_FD[0], line)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def outputs_to_numpy(out):
+    """What TrainStep.step() returned -- (generator losses, discriminator losses, generated dict) -- as {name: host array},
+    float64 kept, everything else float32 (integer tensors: float64, exact).  Copied at once: a replay overwrites them."""
+    import numpy as np
+    g_losses, d_losses, generated = out
+    arrays = {}
+
+    def put(name, t):
+        if isinstance(t, dict):
+            for k, v in t.items():
+                put("%s_%s" % (name, k), v)
+        elif torch.is_tensor(t):
+            dt = np.float64 if t.dtype in (torch.float64, torch.int64, torch.int32) else np.float32
+            arrays[name] = t.detach().cpu().numpy().astype(dt)
+
+    for i, v in enumerate(g_losses):
+        put("loss_generator_%d" % i, v)
+    for i, v in enumerate(d_losses):
+        put("loss_discriminator_%d" % i, v)
+    put("generated", generated)
+    return arrays
+
+
+def dump_outputs(arrays, path):
+    """DIR/<name>.npy for every array; past DUMP_LIMIT_BYTES in all, each array larger than its equal share is replaced by a
+    fixed seeded sample of that many elements (flattened, sorted indices: the same positions in every run)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, a in sorted(arrays.items()):
+        if total > DUMP_LIMIT_BYTES and a.nbytes > share:
+            n = share // a.itemsize
+            idx = np.sort(np.random.RandomState(0).choice(a.size, n, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def graph_phase(args, rank, fallback, run, device):
     """Multi-rank only: capture + time the hipGraph iteration under a deadline.  Returns the elapsed seconds of the K
     timed replays, or None when any rank failed to capture.  If the phase does not finish within MNK_GRAPH_DEADLINE_S
@@ -787,16 +848,21 @@ def main():
             dist.barrier()
             torch.cuda.synchronize(device)
 
+    last_out = {}
+
     def timed(st):
-        """W un-timed + exactly K timed iterations, barrier + synchronize on both sides, MAX over the ranks."""
+        """W un-timed + exactly K timed iterations, barrier + synchronize on both sides, MAX over the ranks.  With
+        --dump-outputs, what the last timed iteration returned is copied to the host (after the clock stopped)."""
         for _ in range(args.warmup):
             st.step(x)
         sync()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            st.step(x)
+            out = st.step(x)
         sync()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:
+            last_out["arrays"] = outputs_to_numpy(out)
         if dist_mode:
             t = torch.tensor([dt], dtype=torch.float64, device=device)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -844,6 +910,7 @@ def main():
             eager = engine.TrainStep(gen, disc, kpd, cfg["train_params"], use_graph=False)
             elapsed = timed(eager)
     ms_per_step = elapsed / args.steps * 1e3
+    dump = last_out.pop("arrays", None)
     global_batch = args.batch * world
     value = global_batch * args.steps / elapsed
 
@@ -1015,6 +1082,7 @@ def main():
             "roofline": roofline, "roofline_all_conv": roofline_all, "roofline_hbm": hbm, "cpu_baseline": cpu, "kernels": kernels,
             "capture_failed": bool(capture_failed),
             "dropin": dropin,
+            "full": bool(args.full),
         }
         if pcie is not None:
             out["pcie_inclusive"] = pcie
@@ -1029,6 +1097,7 @@ def main():
         elif g_elapsed is not None and g_elapsed < elapsed and rank == 0:
             out.update(value=round(global_batch * args.steps / g_elapsed, 2),
                        ms_per_step=round(g_elapsed / args.steps * 1e3, 3))
+            dump = last_out.pop("arrays", dump)      # the reported measurement's last step
             out["config"]["launch"] = "hipGraph replay (RCCL collectives captured); eager: %.3f ms/step" % ms_per_step
     if dist_mode:
         # a peer-to-peer SyncBN exchange that gave up waiting for a rank leaves wrong statistics behind: say so, on every rank
@@ -1051,6 +1120,8 @@ def main():
                 out["capture_failed"] = True
                 out["config"]["launch"] += " -- INVALID: a peer-to-peer exchange timed out (rank %d)" % (out["p2p_error"] - 1)
     if rank == 0:
+        if args.dump_outputs and dump is not None:
+            dump_outputs(dump, args.dump_outputs)
         emit(out)
     if dist_mode:
         dist.destroy_process_group()

@@ -117,3 +117,57 @@ def test_recon_l1_leg_of_the_bench_line(be):
     be.sync()
     assert set(rec) >= {"hip", "cpu_ref", "abs_diff", "max_abs_frame_diff", "sample"}
     assert 0.0 < rec["cpu_ref"] < 1.0 and rec["abs_diff"] < 1e-4 and rec["max_abs_frame_diff"] < 1e-3
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_plain_run_measures_the_headline_only_and_full_keeps_every_leg(monkeypatch):
+    bench = _bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert a.no_profile and a.no_cpu_baseline and not a.dropin and not a.taichi_leg and not a.extra_legs
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out" and a.steps == 3
+    assert not a.no_profile and not a.no_cpu_baseline and a.dropin == 1 and a.taichi_leg == 1 and a.extra_legs == 1
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline", "--dropin", "0"])
+    a = bench.parse()
+    assert a.no_cpu_baseline and a.dropin == 0 and not a.no_profile
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_dump_outputs_writes_every_returned_array_within_the_size_limit(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    bench = _bench_module()
+    g = torch.Generator().manual_seed(0)
+    pred = torch.rand(4, 3, 1, 16, 16, generator=g)
+    out = ([torch.tensor(0.5), torch.tensor(1.5)], [torch.tensor(2.5, dtype=torch.float64)],
+           {"video_prediction": pred, "kp_source": {"mean": torch.rand(4, 1, 10, 2, generator=g)},
+            "index": torch.arange(6), "note": "not an array"})
+    arrays = bench.outputs_to_numpy(out)
+    assert sorted(arrays) == ["generated_index", "generated_kp_source_mean", "generated_video_prediction",
+                              "loss_discriminator_0", "loss_generator_0", "loss_generator_1"]
+    assert arrays["loss_discriminator_0"].dtype == np.float64 and arrays["generated_index"].dtype == np.float64
+    assert arrays["generated_video_prediction"].dtype == np.float32
+    bench.dump_outputs(arrays, str(tmp_path / "all"))
+    got = np.load(tmp_path / "all" / "generated_video_prediction.npy")
+    assert np.array_equal(got, pred.numpy()) and float(np.load(tmp_path / "all" / "loss_generator_1.npy")) == 1.5
+    # past the limit: a fixed sample of each large array, the same positions in every run, all files within the limit
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 6 * 1024)
+    for d in ("a", "b"):
+        bench.dump_outputs(arrays, str(tmp_path / d))
+    sizes = [np.load(p).nbytes for p in (tmp_path / "a").iterdir()]
+    assert len(sizes) == 6 and sum(sizes) <= 6 * 1024
+    sample = np.load(tmp_path / "a" / "generated_video_prediction.npy")
+    assert sample.size == 1024 // 4 and np.isin(sample, pred.numpy().reshape(-1)).all()
+    assert np.array_equal(sample, np.load(tmp_path / "b" / "generated_video_prediction.npy"))

@@ -72,10 +72,9 @@ def test_png_decoder(tmp_path):
         p = os.path.join(tmp_path, "pil_%d.png" % ch)
         Image.fromarray(arr, mode).save(p, optimize=True)
         assert np.array_equal(frames.decode_png(p), arr)
-    ref_png = "/root/reference/data/shapes/train/00000000.png"
-    if os.path.exists(ref_png):
-        with Image.open(ref_png) as im:
-            assert np.array_equal(frames.decode_png(ref_png), np.array(im))
+    ref_png = os.path.join(GOLD, "shapes_train_00000000.png")      # the first video of the reference's data/shapes/train
+    with Image.open(ref_png) as im:
+        assert np.array_equal(frames.decode_png(ref_png), np.array(im))
 
 
 @pytest.mark.parametrize("tag", ["cfg", "crop48", "pad80", "eval"])

@@ -1,6 +1,6 @@
 #!/bin/bash
 # One GPU-box visit that collects everything profiles/ cites for the final build of a round.  Usage: gpu_evidence.sh TAG
-#   tests + smoke, the bench lines (default = BASELINE configs[1] with roofline / cpu_baseline / hot_path_only), rocprofv3
+#   tests + smoke, the bench lines (--full; default workload = BASELINE configs[1], with roofline / cpu_baseline / hot_path_only), rocprofv3
 #   kernel stats (+ steady-state window), FETCH_SIZE / WRITE_SIZE PMC passes (separate runs), an SQ pass over the per-layer
 #   conv bench (MFMA busy, GRBM clock), per-layer conv bench of both configs, batched inference (bair B=512), the
 #   single-rank RCCL exercise of the distributed path.
@@ -37,10 +37,10 @@ P
 find "$OUT" -name "*counter_collection*" -size +8M -delete; find "$OUT" -name "*kernel_trace*" -size +4M -delete
 # bench.py reads roofline.traffic from profiles/: the file of THIS build
 cp "$OUT/pmc_traffic_moving-gif_b32.json" "profiles/${R}_pmc_traffic_moving-gif_b32.json" 2>/dev/null
-echo "== bench (default: moving-gif, roofline + cpu_baseline + hot_path_only)" | tee -a "$S"
-timeout 900 python bench.py > "$OUT/bench_moving-gif_b32.json" 2> "$OUT/bench.err"; echo "rc=$?" | tee -a "$S"; cut -c1-900 "$OUT/bench_moving-gif_b32.json" | tee -a "$S"
-timeout 400 python bench.py --config taichi --no-cpu-baseline > "$OUT/bench_taichi_b32.json" 2> "$OUT/bench_taichi.err"; echo "taichi rc=$?" | tee -a "$S"; cut -c1-300 "$OUT/bench_taichi_b32.json" | tee -a "$S"
-timeout 300 python bench.py --config vox --size 256 --batch 8 --no-cpu-baseline > "$OUT/bench_vox256_b8.json" 2> "$OUT/bench_vox.err"; echo "vox 256 rc=$?" | tee -a "$S"; cut -c1-300 "$OUT/bench_vox256_b8.json" | tee -a "$S"
+echo "== bench --full (moving-gif: roofline + cpu_baseline + hot_path_only)" | tee -a "$S"
+timeout 900 python bench.py --full > "$OUT/bench_moving-gif_b32.json" 2> "$OUT/bench.err"; echo "rc=$?" | tee -a "$S"; cut -c1-900 "$OUT/bench_moving-gif_b32.json" | tee -a "$S"
+timeout 400 python bench.py --full --config taichi --no-cpu-baseline > "$OUT/bench_taichi_b32.json" 2> "$OUT/bench_taichi.err"; echo "taichi rc=$?" | tee -a "$S"; cut -c1-300 "$OUT/bench_taichi_b32.json" | tee -a "$S"
+timeout 300 python bench.py --full --config vox --size 256 --batch 8 --no-cpu-baseline > "$OUT/bench_vox256_b8.json" 2> "$OUT/bench_vox.err"; echo "vox 256 rc=$?" | tee -a "$S"; cut -c1-300 "$OUT/bench_vox256_b8.json" | tee -a "$S"
 echo "== rocprofv3 kernel stats (eager iteration)" | tee -a "$S"
 CMD="env $EAGER_ENV python $PWD/bench.py --steps 5 --warmup 2 --graph 0 --no-cpu-baseline --no-profile --dropin 0"
 ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OLDPWD/$OUT/prof" -o bench -- $CMD > "$OLDPWD/$OUT/rocprof.log" 2>&1 ); echo "rocprof rc=$?" | tee -a "$S"
