@@ -29,14 +29,17 @@ mnk_adam_multi on their own state tensors (mnk.optim.AdoptedAdam: one launch tha
 mnk.optim.MnkAdam objects own the flat buffers themselves.
 
 Anything unexpected -- evaluation mode, no_grad, gradients that were not zeroed, a discriminator call on tensors that are not
-this iteration's outputs, changed discriminator weights in between, several driving frames, a process group -- falls back
-to calling the wrapped module as it is.  MNK_DROPIN_GRAPH=0 switches the runner off, =phases runs the three phases as eager
+this iteration's outputs, changed discriminator weights in between, several driving frames, a process group,
+train_params['detach_kp_discriminator'] = False, a failed warm-up before the capture -- falls back to calling the wrapped module
+as it is.  The backward pass of a fall-back leaves every gradient in p.grad (the sinks take weight gradients only inside phases
+B / C: mnk.optim.FlatGrads.deferring).  MNK_DROPIN_GRAPH=0 switches the runner off, =phases runs the three phases as eager
 launches (what the CPU-emulator tests exercise; also the form used when the device has no graph support).
 
 Returned tensors of the graph form (loss vectors, `generated`, `kp_joined`) are static buffers that the next
 generator_full_par(x) call overwrites -- the loop's `.cpu()` copies and logger calls read them before that.
 """
 import gc
+import warnings
 import weakref
 
 import torch
@@ -72,7 +75,7 @@ class _PhaseFn(torch.autograd.Function):
 class _Program:
     """one captured iteration: three hipGraphs over one memory pool and their static tensors"""
     __slots__ = ("x", "gA", "gB", "gC", "g_vec", "d_vec", "g_grads", "d_grads", "generated", "kp_joined", "grads_g", "grads_d",
-                 "reg_version", "keep")
+                 "reg_version", "ptrs", "keep")
 
 
 class TrainPairRunner:
@@ -123,6 +126,10 @@ class TrainPairRunner:
 
     def _ready(self, x):
         if not torch.is_grad_enabled() or mdist.initialized():
+            return False
+        # detach_kp_discriminator = False: the discriminator loss also reaches the key-point detector through the graph that the
+        # generator pass retained (train.py:117,131), before its optimiser steps -- not served (and no sinks registered for it)
+        if not self.tp["detach_kp_discriminator"]:
             return False
         if not (self.kp.training and self.gen.training and self.disc.training):
             return False
@@ -175,29 +182,16 @@ class TrainPairRunner:
         if tp["loss_weights"]["reconstruction_deformed"] != 0:       # the only term of L_G that does not pass the cut: vector 0
             roots.append(st["g_vec"][0])
             root_grads.append(grads[0])
-        torch.autograd.backward(roots, root_grads, inputs=self.g_params + self.k_params,
-                                retain_graph=not tp["detach_kp_discriminator"])
+        with self.owners["g"].deferring(), self.owners["k"].deferring():
+            torch.autograd.backward(roots, root_grads, inputs=self.g_params + self.k_params)
         self.owners["g"].materialize_grads()
         self.owners["k"].materialize_grads()
 
     def _phase_c(self, st, grads):
-        """dL_D / d(discriminator parameters) (and, unless detach_kp_discriminator, the key-point detector's share) through the
-        discriminator graph phase B retained"""
-        tp = self.tp
-        if tp["detach_kp_discriminator"]:
-            with mops.no_leaf_input_grads():
-                torch.autograd.backward(st["d_vec"], list(grads), inputs=self.d_params)
-        else:
-            kl = [st["kp_leaf"][k] for k in st["names"]]
-            for t in kl:
-                t.grad = None
-            torch.autograd.backward(st["d_vec"], list(grads), inputs=self.d_params + kl)
-            back = [(st["kp_joined"][k], st["kp_leaf"][k].grad) for k in st["names"] if st["kp_leaf"][k].grad is not None]
-            if back:
-                # (the key-point detector has not stepped yet, train.py:133-135: a second contribution to its gradients -- the
-                # sinks' slow path adds it, FlatGrads.add_to_sink)
-                torch.autograd.backward([t for t, _ in back], [g for _, g in back], inputs=self.k_params)
-                self.owners["k"].materialize_grads()
+        """dL_D / d(discriminator parameters) through the discriminator graph phase B retained (detach_kp_discriminator is True
+        here: _ready refuses the other case)"""
+        with mops.no_leaf_input_grads(), self.owners["d"].deferring():
+            torch.autograd.backward(st["d_vec"], list(grads), inputs=self.d_params)
         self.owners["d"].materialize_grads()
 
     # ---- capture -----------------------------------------------------------------------------------------------------------------
@@ -208,7 +202,14 @@ class TrainPairRunner:
         for o in self.owners.values():
             o.begin_pass()
 
+    def _tensor_ptrs(self):
+        """data pointers of every parameter and buffer of the three networks: a captured program reads them by address, and
+        `p.data = ...` / `module.float()` swap the storage without a `_version` bump"""
+        return tuple(t.data_ptr() for m in (self.kp, self.gen, self.disc) for t in (*m.parameters(), *m.buffers()))
+
     def _capture(self, x):
+        """the three phases captured as one _Program, or None when the warm-up before the capture failed (the caller falls back
+        to the modules as they are; buffers and gradients as they were before the call)"""
         b = int(x["source"].shape[0])
         dev = self.device
         prog = _Program()
@@ -219,20 +220,32 @@ class TrainPairRunner:
         n_g = None
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for it in range(2):          # sizes scratch buffers, creates the packed weights and every descriptor table
-                st = self._phase_a(prog.x)
-                n_g, n_d = len(st["g_vec"]), len(st["d_vec"])
-                ones_g = [torch.full((b,), 1.0 / b, device=dev) for _ in range(n_g)]
-                ones_d = [torch.full((b,), 1.0 / b, device=dev) for _ in range(n_d)]
-                self._phase_b(st, ones_g)
-                self._phase_c(st, ones_d)
-                del st
-                self._clear_grads()
-            prog.g_grads = [torch.full((b,), 1.0 / b, device=dev) for _ in range(n_g)]
-            prog.d_grads = [torch.full((b,), 1.0 / b, device=dev) for _ in range(n_d)]
-            mops.repack_registered()     # every packed layout fresh: no pack launch is recorded into phase A
-        torch.cuda.current_stream().wait_stream(side)
+        try:
+            with torch.cuda.stream(side):
+                for it in range(2):      # sizes scratch buffers, creates the packed weights and every descriptor table
+                    st = self._phase_a(prog.x)
+                    n_g, n_d = len(st["g_vec"]), len(st["d_vec"])
+                    ones_g = [torch.full((b,), 1.0 / b, device=dev) for _ in range(n_g)]
+                    ones_d = [torch.full((b,), 1.0 / b, device=dev) for _ in range(n_d)]
+                    self._phase_b(st, ones_g)
+                    self._phase_c(st, ones_d)
+                    del st
+                    self._clear_grads()
+                prog.g_grads = [torch.full((b,), 1.0 / b, device=dev) for _ in range(n_g)]
+                prog.d_grads = [torch.full((b,), 1.0 / b, device=dev) for _ in range(n_d)]
+                mops.repack_registered()     # every packed layout fresh: no pack launch is recorded into phase A
+        except Exception as e:           # (no capture has begun: nothing is left half-recorded)
+            warnings.warn("mnk.dropin: the warm-up before the capture failed (%s: %s); the wrapped modules run as they are"
+                          % (type(e).__name__, e))
+            return None
+        finally:
+            torch.cuda.current_stream().wait_stream(side)
+            st = None                    # (the autograd graph of a failed warm-up iteration)
+            self._clear_grads()
+            mops.clear_dz_stats()
+            with torch.no_grad():
+                for t, c in snap:
+                    t.copy_(c)
         torch.cuda.synchronize()
         gc.collect()
         torch.cuda.empty_cache()
@@ -264,8 +277,7 @@ class TrainPairRunner:
                 for p, _ in prog.grads_g:
                     p.grad = None
                 prog.gC = captured(lambda: self._phase_c(state, prog.d_grads))
-                own = (("d", self.d_params),) if self.tp["detach_kp_discriminator"] else (("d", self.d_params), ("k", self.k_params))
-                prog.grads_d = [(p, self.owners[n].sink(p)) for n, ps in own for p in ps if p.grad is not None]
+                prog.grads_d = [(p, self.owners["d"].sink(p)) for p in self.d_params if p.grad is not None]
         except BaseException:
             if current[0] is not None:
                 try:
@@ -287,6 +299,7 @@ class TrainPairRunner:
             for t, c in snap:
                 t.copy_(c)
         prog.reg_version = mops.pack_registry_version()
+        prog.ptrs = self._tensor_ptrs()
         self.stats["captures"] += 1
         return prog
 
@@ -308,12 +321,18 @@ class TrainPairRunner:
         if self.use_graph:
             key = tuple(x["source"].shape)
             prog = self.programs.get(key)
-            if prog is not None and prog.reg_version != mops.pack_registry_version():
-                prog = None              # packed-weight buffers were re-created (parameters moved): their addresses are in the graphs
+            if prog is not None and (prog.reg_version != mops.pack_registry_version() or prog.ptrs != self._tensor_ptrs()):
+                prog = None              # packed-weight buffers were re-created / a storage was swapped: addresses are in the graphs
             if prog is None:
                 if len(self.programs) >= 4:
                     self.programs.clear()
-                prog = self.programs[key] = self._capture(x)
+                self.programs.pop(key, None)
+                prog = self._capture(x)
+                if prog is None:
+                    self.stats["fallbacks"] += 1
+                    self.cur = self._last = None
+                    return NotImplemented
+                self.programs[key] = prog
             for k in ("source", "video"):
                 prog.x[k].copy_(x[k], non_blocking=True)
             mops.repack_registered(only_if_stale=True)       # a stock optimiser stepped: one pack launch; MnkAdam / AdoptedAdam: none
@@ -347,8 +366,6 @@ class TrainPairRunner:
               and not self._done["d"]
               and all(p._version == v for p, v in zip(self.d_params, last["d_versions"]))
               and all(p.grad is None for p in self.d_params))
-        if ok and not self.tp["detach_kp_discriminator"]:
-            ok = all(p.grad is None for p in self.k_params)
         if not ok:
             self.stats["d_fallbacks"] += 1
             return NotImplemented
@@ -467,8 +484,9 @@ class EvalRunner:
         return obj
 
     def _fingerprint(self, module):
-        return (mops._PACK_EPOCH[0], mops._BN_EVAL_EPOCH[0], tuple(p._version for p in module.parameters()),
-                tuple(b._version for b in module.buffers()))
+        # (data_ptr: `p.data = ...`, module.float() / .to() swap the storage the graph reads and keep _version)
+        return (mops._PACK_EPOCH[0], mops._BN_EVAL_EPOCH[0], tuple((p._version, p.data_ptr()) for p in module.parameters()),
+                tuple((b._version, b.data_ptr()) for b in module.buffers()))
 
     def __call__(self, inputs, kwargs, device):
         module = self._module()

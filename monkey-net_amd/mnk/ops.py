@@ -321,6 +321,13 @@ def sink_owner(p):
     return r() if r is not None else None
 
 
+def wgrad_sink_owner(p):
+    """the owner whose sink takes p's weight gradient in THIS backward pass, or None (autograd gets dW): an MnkAdam always, a
+    mnk.optim.GradSinks only while the drop-in runner's phase B / C runs (FlatGrads.defers_wgrad)"""
+    o = sink_owner(p)
+    return o if o is not None and o.defers_wgrad else None
+
+
 def pack_registry_version():
     return _PACK_REG_VERSION[0]
 
@@ -793,7 +800,7 @@ class Conv3x3Fn(_Fn):
         if ctx.needs_input_grad[2]:
             # an optimiser of mnk.optim owns this parameter: the GEMM writes (the partials of) its gradient towards the
             # optimiser's flat buffer and the split reduction waits for the one launch that serves every layer
-            owner = sink_owner(weight)
+            owner = wgrad_sink_owner(weight)
             taken = [False, False]
             if owner is not None:
                 for i, (src, cs, cc) in enumerate(((x0, 0, c0), (x1, c0, c1))):
@@ -1205,7 +1212,7 @@ class ConvKxKFn(_Fn):
             _call("mnk_conv2d_fwd", dy, _p(dy), dy.shape[-1], cout, None, 0, 0, 2, ho, wo, kh, kw, kh - 1 - pad, _p(wp), None,
                   None, 0, _p(dx), dx.shape[-1], n, hi, wi, cin, _p(ws), nws, None)
         if ctx.needs_input_grad[1] and not _SKIP_PARAM_GRADS[0]:
-            owner = sink_owner(weight)
+            owner = wgrad_sink_owner(weight)
             if owner is None or not owner.reducer.wgrad(weight, x, x.shape[-1], cin, 0, hi, wi, kh, kw, pad, dy,
                                                         dy.shape[-1], cout, cin, 0, n, ho, wo):
                 dw = torch.empty_like(weight)

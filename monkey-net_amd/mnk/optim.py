@@ -14,6 +14,7 @@ slice per parameter:
   copy back; the division by the world size is folded into the update (`grad_scale`);
 * learning rate, step count and bias corrections live in device memory, so a captured hipGraph follows a scheduler.
 """
+import contextlib
 import ctypes
 import weakref
 
@@ -343,6 +344,20 @@ class FlatGrads:
         self.reducer.drop()
         self._written.clear()
 
+    # the convolutions' backward hands dW to the sinks (mnk.ops.wgrad_sink_owner) only while this is True.  MnkAdam: always -- its
+    # step() materialises.  GradSinks: only inside deferring(), i.e. the drop-in runner's phases B / C, which materialise before
+    # they return; any other backward pass over the same parameters (a fall-back to the modules as they are) takes the per-layer
+    # path and autograd puts dW into p.grad, where a stock optimiser, clip_grad_norm_ or any other reader finds it
+    defers_wgrad = True
+
+    @contextlib.contextmanager
+    def deferring(self):
+        prev, self.defers_wgrad = self.defers_wgrad, True
+        try:
+            yield self
+        finally:
+            self.defers_wgrad = prev
+
 
 class GradSinks(FlatGrads):
     """FlatGrads of a network whose optimiser is not ours (see FlatGrads)."""
@@ -350,6 +365,7 @@ class GradSinks(FlatGrads):
     def __init__(self, params):
         self._init_sinks(list(params))
         self._mnk_owns_exchange = False
+        self.defers_wgrad = False
 
 
 class MnkAdam(torch.optim.Optimizer, FlatGrads):
