@@ -718,6 +718,44 @@ typedef struct MnkAugJob {
 int mnk_frames_augment(const unsigned char* pool, const MnkAugJob* jobs_device, int njobs, int any_rotation, double* rot_range,
                        int any_contrast, int* contrast_mean, int H, int W, int Cout, float* out, void* stream);
 
+/* ---- GRU key-point predictor (modules/prediction_module.py:14-17 nn.GRU(batch_first=True) + nn.Linear; trained by
+ * prediction.py:97-107, rolled out by prediction.py:116-132) -------------------------------------------------------------
+ * PyTorch GRU semantics, gate order (r, z, n), weights as nn.GRU keeps them (W_ih [3H, I], W_hh [3H, H], no repacking).
+ * Row-major fp32 matrices.  A GEMM operand may have GROUPED rows: stored row r lies (r / grp) * ld_grp + (r % grp) * ld floats
+ * from its base (grp <= 0: plain rows r * ld) -- a [B, T, F] tensor with any batch / time strides is read in (b, t) or (t, b)
+ * row order without a copy.
+ * Per-step buffers of the recurrence: gates [B][4H] = r | z | n | hn (hn = h W_hn^T + b_hn), dGi / dGh [B][3H] (gradients of
+ * x W_ih^T + b_ih and of h W_hh^T + b_hh), carry [B][H].  Deterministic: no atomics, split-K partials summed in a fixed order. */
+size_t mnk_gru_gemm_workspace_floats(int M, int N, int K);
+/* C[m][n] = sum_k op(A)[m][k] op(B)[k][n] (+ bias[n]); A stored [M][K] (transA = 0) or [K][M] (1); B stored [K][N] (transB = 0)
+ * or [N][K] (1: an nn.Linear / nn.GRU weight).  Replaces the input projection of nn.GRU for all time steps at once
+ * (x W_ih^T + b_ih), nn.Linear of prediction_module.py:23 and their backward GEMMs (dW_ih, dW_hh = sum_t dGh_t^T h_{t-1}, dW_lin,
+ * dX, dH). */
+int mnk_gru_gemm(int transA, int transB, int M, int N, int K, const float* A, long lda, int a_grp, long lda_grp, const float* B,
+                 long ldb, int b_grp, long ldb_grp, const float* bias, float* C, long ldc, float* ws, size_t ws_floats,
+                 void* stream);
+/* out[c] = sum_r x[r * ld + c] (bias gradients of nn.GRU / nn.Linear), two stages in a fixed order */
+size_t mnk_gru_colsum_workspace_floats(long rows, int cols);
+int mnk_gru_colsum(const float* x, long ld, long rows, int cols, float* out, float* ws, size_t ws_floats, void* stream);
+/* one time step of nn.GRU (prediction_module.py:20): h = GRUCell(gi = x_t W_ih^T + b_ih, h_prev); `gates` (may be NULL under
+ * no_grad) receives r, z, n, hn for the backward pass.  Batches of at most a few rows take a GEMV form (tuning value
+ * "gru_gemv_rows"). */
+int mnk_gru_step_fwd(const float* h_prev, long ld_hp, const float* w_hh, const float* b_hh, const float* gi, long ld_gi, float* h,
+                     long ld_h, float* gates, int B, int H, void* stream);
+/* backward of the last step's gates: dh = dy (may be NULL) + dh_n (may be NULL, [B][H]) -> dgi, dgh, carry = dh * z */
+int mnk_gru_gates_bwd(const float* dy, long ld_dy, const float* dh_n, const float* gates, const float* h_prev, long ld_hp, float* dgi,
+                      float* dgh, float* carry, int B, int H, void* stream);
+/* dh_{t-1} = dgh_t W_hh + carry + dy_prev (may be NULL), written to dh_out (may be NULL); with gates_prev (step t - 1's gates,
+ * h_pp = h_{t-2}) the gate backward of step t - 1 follows in the same launch: dgi_prev, dgh_prev, carry (in place) */
+int mnk_gru_step_bwd(const float* dgh, const float* w_hh, float* carry, const float* dy_prev, long ld_dy, const float* gates_prev,
+                     const float* h_pp, long ld_hp, float* dgi_prev, float* dgh_prev, float* dh_out, long ld_out, int B, int H,
+                     void* stream);
+/* prediction_module.py:33-42 on y [rows][num_kp][feats]: mean [rows][num_kp][2] = tanh(y[..., :2]); with has_var (feats >= 6)
+ * var [rows][num_kp][2][2] = V^T V, V = y[..., 2:6] as 2x2.  Backward: dy from dmean / dvar (either may be NULL: zero) */
+int mnk_gru_head_fwd(const float* y, long rows, int num_kp, int feats, int has_var, float* mean, float* var, void* stream);
+int mnk_gru_head_bwd(const float* y, const float* dmean, const float* dvar, long rows, int num_kp, int feats, int has_var, float* dy,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

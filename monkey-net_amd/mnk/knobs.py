@@ -36,6 +36,9 @@ KNOBS = {
                             "hipGraph with frozen weights and replayed (mnk.dropin.EvalRunner); 0: eager launches"),
     "MNK_ADOPT_ADAM": ("1", "a stock torch.optim.Adam over a network whose gradients the drop-in runner keeps in one flat buffer is "
                             "stepped by mnk_adam_multi on the optimiser's own state tensors (mnk.optim.AdoptedAdam); 0: the stock step"),
+    "MNK_NATIVE_PREDICTION": ("0", "1: `import modules.prediction_module` (prediction.py:10) resolves to mnk.predictor, the key-point "
+                                   "GRU on the library's kernels, ahead of the reference's own modules/prediction_module.py; 0: the "
+                                   "reference's file, found behind this package on sys.path"),
     "MNK_GRAD_OVERLAP": ("1", "MnkAdam: the generator-side gradient exchange runs next to the discriminator backward when there is "
                               "more than one rank (force: also on one rank); GradAverager: a bucket's all-reduce starts when its "
                               "last gradient is written; 0: in-order exchanges"),
