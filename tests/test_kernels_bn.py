@@ -4,6 +4,7 @@ import torch
 import torch.nn.functional as F
 
 from _util import to_nhwc, from_nhwc, ceil4, relerr, maxerr
+from _guard import be  # noqa: F401  (guard-banded buffers, checked calls)
 
 
 @pytest.mark.parametrize("shape", [(2, 5, 6, 4), (3, 45, 4, 6), (2, 300, 2, 2), (1, 64, 16, 16)])

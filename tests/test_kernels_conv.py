@@ -5,6 +5,7 @@ import torch
 import torch.nn.functional as F
 
 from _util import to_nhwc, from_nhwc, ceil4, relerr, maxerr
+from _guard import be  # noqa: F401  (guard-banded buffers, checked calls)
 
 @pytest.fixture(params=["f32-mfma", "bf16x3"], autouse=True)
 def gemm_mode(request, be):

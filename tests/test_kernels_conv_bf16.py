@@ -14,7 +14,8 @@ def test_the_bf16_split_gemm_is_as_accurate_as_the_fp32_mfma_chain():
     fp32 MFMA chain (measured: 0.8 ... 1.05 x -- each bf16 x bf16 product is exact, the three dropped cross terms are below the
     rounding of an fp32 product, and the MFMA adds in fp32 either way)."""
     from conftest import Backend
-    be = Backend("hip")
+    from _guard import guarded
+    be = guarded(Backend("hip"))
     shapes = [(4, 32, 32, 64, 0, 128), (4, 16, 16, 128, 0, 256), (4, 8, 8, 256, 0, 512), (4, 4, 4, 512, 0, 1024),
               (4, 2, 2, 1024, 0, 1024), (4, 32, 32, 138, 128, 64), (4, 64, 64, 64, 0, 64), (4, 8, 8, 522, 0, 128)]
     rows = []

@@ -4,6 +4,7 @@ import torch
 import torch.nn.functional as F
 
 from _util import to_nhwc, from_nhwc, ceil4, relerr, maxerr
+from _guard import be  # noqa: F401  (guard-banded buffers, checked calls)
 from oracle import restate, cases
 
 

@@ -4,6 +4,7 @@ import pytest
 import torch
 
 from _util import to_nhwc, from_nhwc, ceil4, relerr, maxerr
+from _guard import be  # noqa: F401  (guard-banded buffers, checked calls)
 
 
 @pytest.mark.parametrize("shape", [(3, 5, 7, 6), (2, 64, 30, 30), (1, 13, 4, 4), (4, 256, 2, 2)])

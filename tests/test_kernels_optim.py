@@ -9,6 +9,7 @@ import torch
 import torch.nn.functional as F
 
 from _util import to_nhwc, ceil4, relerr
+from _guard import be  # noqa: F401  (guard-banded buffers, checked calls)
 from test_kernels_conv import CASES, HALO_CASES, WFAST_CASES, K4_CASES, _inputs
 
 
@@ -369,8 +370,7 @@ def test_table_upload_through_kernel_arguments(be):
     g = torch.Generator().manual_seed(1)
     for nbytes in (16, 3584, 3600, 12000):
         host = torch.randint(0, 256, (nbytes,), generator=g, dtype=torch.uint8).numpy()
-        dev = be.zeros((nbytes + 15) // 16 * 16 // 4).view(torch.uint8) if be.kind == "emu" else \
-            torch.zeros((nbytes + 15) // 16 * 16, dtype=torch.uint8, device=be.device)
+        dev = be.empty_int((nbytes + 15) // 16 * 16, dtype=torch.uint8).zero_()
         be.lib.call("mnk_table_upload", host.ctypes.data, dev.data_ptr(), nbytes, be.stream())
         be.sync()
         assert bytes(dev.cpu().numpy()[:nbytes]) == bytes(host)

@@ -19,6 +19,7 @@ import pytest
 import torch
 
 from oracle import cases
+from _guard import be  # noqa: F401  (guard-banded buffers, checked calls)
 from test_modules import build, load
 
 BOUNDARY_PX = 1e-4
@@ -41,7 +42,7 @@ def test_heatmap_argmax_kernel(be, n, h, w, k, ld):
     p1 = int(flat[0, :, 1].argmax())
     if p1 > 0:
         flat[0, 0, 1] = flat[0, p1, 1]
-    idx = torch.empty(n, k, dtype=torch.int32, device=be.device)
+    idx = be.empty_int(n, k, dtype=torch.int32)
     be.call("mnk_heatmap_argmax", be.t(heat), ld, n, h, w, k, idx)
     be.sync()
     want = _first_argmax(flat[:, :, :k].permute(0, 2, 1))
@@ -74,7 +75,7 @@ def test_kp_pixel_index_kernel_at_a_frame_size_that_is_not_a_power_of_two(be):
         pts.append(low)
     pts.append(torch.rand(4000, 2, generator=g) * 2.2 - 1.1)
     mean = torch.cat(pts)
-    out = torch.empty(mean.shape, dtype=torch.int32, device=be.device)
+    out = be.empty_int(mean.shape, dtype=torch.int32)
     be.call("mnk_kp_pixel_index", be.t(mean), mean.shape[0], W, H, out)
     be.sync()
     want = _numpy_pixel_index(mean, W, H)
@@ -94,7 +95,7 @@ def test_kp_pixel_index_kernel(be):
     rnd = torch.rand(500, 2, generator=g) * 2.4 - 1.2                                    # incl. points outside the frame
     clearly = on - 1e-3
     mean = torch.cat([on, below, clearly, rnd])
-    out = torch.empty(mean.shape, dtype=torch.int32, device=be.device)
+    out = be.empty_int(mean.shape, dtype=torch.int32)
     be.call("mnk_kp_pixel_index", be.t(mean), mean.shape[0], W, H, out)
     be.sync()
     want = _numpy_pixel_index(mean, W, H)                                                # logger.py:99-100 as numpy evaluates it

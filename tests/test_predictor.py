@@ -9,6 +9,7 @@ import sys
 import pytest
 import torch
 from torch import nn
+from _guard import be  # noqa: F401  (guard-banded buffers, checked calls)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = os.environ.get("MNK_REFERENCE_ROOT", "/root/reference")
