@@ -363,8 +363,8 @@ int mnk_wgrad_reduce_multi(const MnkWgradReduceDesc* descs_device, int n, int to
  * layer through mnk_conv2d_wgrad), `splits` and `part_floats` -> give every job its operands and a `part` buffer ->
  * mnk_wgrad_grouped_build serialises the launch tables into HOST memory (mnk_wgrad_grouped_table_bytes(n)); copy them
  * to the device -> mnk_wgrad_grouped_launch(device copy, host copy).  The partials are tap-major [split][tap][Cout][C]:
- * reduce them with mnk_wgrad_reduce_multi (layout 0, `splits` as planned; layout 2 for variants with variant % 4 == 3: the
- * sub-pixel form).  Variants >= 16: narrow 3x3 layers (C, Cout <= 64) on the nine-tap 16x16-MFMA kernel, grouped the same
+ * reduce them with mnk_wgrad_reduce_multi (`layout` and `splits` as planned: layout 0, or 2 for the sub-pixel form,
+ * variant % 4 == 3).  Variants >= 16: narrow 3x3 layers (C, Cout <= 64) on the nine-tap 16x16-MFMA kernel, grouped the same
  * way (~128 blocks per layer instead of the 512 a layer needs alone: the eight 45 -> 45 convolutions of the refinement
  * stack write 9 instead of 37 MB of partials each); their partials are tap-major too (layout 0). */
 typedef struct MnkWgradJob {
@@ -375,7 +375,7 @@ typedef struct MnkWgradJob {
     int ld_x, C, flags, ld_dy, Cout;         /* flags: MNK_CONV_UPSAMPLED | MNK_CONV_CLEAN_PADS */
     int N, Ho, Wo, Hi, Wi, kh, kw, pad;
     int variant, splits;                     /* out (plan) */
-    int reserved;
+    int layout;                              /* out (plan): MnkWgradPlan::layout of the partials (0, or 2: sub-pixel form) */
 } MnkWgradJob;
 int mnk_wgrad_grouped_plan(MnkWgradJob* jobs, int n);
 size_t mnk_wgrad_grouped_table_bytes(int n);

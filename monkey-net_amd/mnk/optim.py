@@ -37,7 +37,7 @@ REDUCE_DESC = np.dtype([("part", "<u8"), ("dw", "<u8"), ("layout", "<i4"), ("spl
 JOB = np.dtype([("x", "<u8"), ("dy", "<u8"), ("part", "<u8"), ("part_floats", "<u8"), ("ld_x", "<i4"), ("C", "<i4"),
                 ("flags", "<i4"), ("ld_dy", "<i4"), ("Cout", "<i4"), ("N", "<i4"), ("Ho", "<i4"), ("Wo", "<i4"), ("Hi", "<i4"),
                 ("Wi", "<i4"), ("kh", "<i4"), ("kw", "<i4"), ("pad", "<i4"), ("variant", "<i4"), ("splits", "<i4"),
-                ("reserved", "<i4")])
+                ("layout", "<i4")])
 
 
 class _Plan(ctypes.Structure):
@@ -103,15 +103,11 @@ class DeferredReducer:
         lib = _lib.lib()
         job = np.zeros(1, dtype=JOB)
         job[0] = (0, 0, 0, 0, ld_x, c, flags, ld_dy, cout, n, ho, wo, hi, wi, kh, kw, pad, 0, 0, 0)
-        grouped = True
-        if grouped:
-            if lib.query("mnk_wgrad_grouped_plan", job.ctypes.data, 1) != 0:
-                raise _lib.MnkError("mnk_wgrad_grouped_plan failed: %s" % lib.cdll.mnk_last_error().decode())
-            grouped = int(job["variant"][0]) >= 0
-        if grouped:       # variant % 4 == 3: the sub-pixel form of an up-sampled layer (16 pseudo taps, layout 2);
-            v = int(job["variant"][0])                  # variants >= 16: the nine-tap 16x16 kernel (tap-major partials too)
-            layout = 2 if (v < 16 and v % 4 == 3) else 0
-            splits, nfloats = int(job["splits"][0]), int(job["part_floats"][0])
+        if lib.query("mnk_wgrad_grouped_plan", job.ctypes.data, 1) != 0:
+            raise _lib.MnkError("mnk_wgrad_grouped_plan failed: %s" % lib.cdll.mnk_last_error().decode())
+        grouped = int(job["variant"][0]) >= 0
+        if grouped:       # tap-major or nine-tap 16x16 kernel; layout 2: the sub-pixel form of an up-sampled layer (16 pseudo taps)
+            layout, splits, nfloats = int(job["layout"][0]), int(job["splits"][0]), int(job["part_floats"][0])
         else:
             plan = _Plan()
             if lib.query("mnk_conv2d_wgrad_plan2", n, ho, wo, c, cout, kh, kw, pad, ld_x, flags, ctypes.byref(plan)) != 0:

@@ -101,7 +101,7 @@ def test_deferred_wgrad_of_many_layers_reduced_in_one_launch(be, accumulate):
 
 
 def _fold16(acc):
-    """(16, ...) pseudo-tap sums of the sub-pixel form -> (9, ...) kernel taps (csrc/conv3x3.hip: up_fold)"""
+    """(16, ...) pseudo-tap sums of the sub-pixel form -> (9, ...) kernel taps (csrc/pack_tile.h: up_fold)"""
     def pairs(k):
         return ((0, 0 if k == 0 else 1), (1, 1 if k == 2 else 0))
     out = []
@@ -262,7 +262,7 @@ def test_adam_multi_matches_torch_adam_and_emits_the_packs(be, lr_drop):
 JOB = np.dtype([("x", "<u8"), ("dy", "<u8"), ("part", "<u8"), ("part_floats", "<u8"), ("ld_x", "<i4"), ("C", "<i4"),
                 ("flags", "<i4"), ("ld_dy", "<i4"), ("Cout", "<i4"), ("N", "<i4"), ("Ho", "<i4"), ("Wo", "<i4"), ("Hi", "<i4"),
                 ("Wi", "<i4"), ("kh", "<i4"), ("kw", "<i4"), ("pad", "<i4"), ("variant", "<i4"), ("splits", "<i4"),
-                ("reserved", "<i4")])
+                ("layout", "<i4")])
 
 
 @pytest.mark.parametrize("subpixel", [1, 0], ids=["up-layers-subpixel", "up-layers-upsampled-view"])
@@ -331,8 +331,7 @@ def _grouped_weight_gradients(be, subpixel):
         parts.append(part)
         grouped["part"][k] = part.data_ptr()
         DW, cin_total, c_start, c_cnt, cout, ntaps, _ = meta[i]
-        v = int(grouped["variant"][k])
-        rows.append((part.data_ptr(), DW.data_ptr(), 2 if (v < 16 and v % 4 == 3) else 0, int(grouped["splits"][k]),
+        rows.append((part.data_ptr(), DW.data_ptr(), int(grouped["layout"][k]), int(grouped["splits"][k]),
                      ntaps, cout, c_cnt, cin_total, c_start, 0, blocks, 0))
         blocks += be.query("mnk_wgrad_reduce_blocks", int(grouped["splits"][k]), cout, c_cnt)
     nbytes = be.query("mnk_wgrad_grouped_table_bytes", len(grouped))
