@@ -1473,6 +1473,29 @@ static Plan make_plan(long M, int Cout, int chunks, int ntaps = 9, int phases = 
     return p;
 }
 
+// What one forward / data-gradient launch needs: its plan and the floats of the caller's two buffers -- the split-K partials
+// (0: the plan does not split) and the BatchNorm statistics (0: a split plan without splitk_stats).  The size queries answer
+// from it and conv2d_fwd_impl launches from it.
+struct Launch {
+    Plan p;
+    size_t ws_floats, stats_floats;
+};
+// (ntaps, phases): the form's geometry -- (kh * kw, 1); sub-pixel forward (4, 4), sub-pixel data gradient (16, 1).  (H, W): the
+// map ONE phase writes.  A shape no launch takes: all zero, and no plan is made.
+static Launch plan_launch(int ntaps, int phases, int N, int H, int W, int C0, int C1, int Cout) {
+    Launch l{};
+    if (N <= 0 || H <= 0 || W <= 0 || C0 <= 0 || C1 < 0 || Cout <= 0 || ntaps <= 0) return l;
+    const long M = (long)N * H * W;
+    const int ldw = round_up(Cout, 4);
+    l.p = make_plan(M, Cout, (round_up(C0, 16) + (C1 > 0 ? round_up(C1, 16) : 0)) / 16, ntaps, phases);
+    if (l.p.splits > 1) {
+        l.ws_floats = (size_t)l.p.splits * phases * M * l.p.ldw;
+        l.stats_floats = g_splitk_stats ? (size_t)make_rsmap(M * phases, ldw).row_blocks * 2 * ldw : 0;
+    } else
+        l.stats_floats = (size_t)phases * l.p.gm * 2 * ldw;
+    return l;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1537,22 +1560,50 @@ int mnk_conv3x3_pack_multi(const MnkPackDesc* descs_device, int n, int total_til
 }
 
 size_t mnk_conv2d_workspace_floats(int N, int Ho, int Wo, int C0, int C1, int Cout, int ntaps) {
-    if (N <= 0 || Ho <= 0 || Wo <= 0 || C0 <= 0 || C1 < 0 || Cout <= 0 || ntaps <= 0) return 0;
-    const int chunks = (round_up(C0, 16) + (C1 > 0 ? round_up(C1, 16) : 0)) / 16;
-    Plan p = make_plan((long)N * Ho * Wo, Cout, chunks, ntaps);
-    return p.splits > 1 ? (size_t)p.splits * N * Ho * Wo * p.ldw : 0;
+    return plan_launch(ntaps, 1, N, Ho, Wo, C0, C1, Cout).ws_floats;
 }
-
 size_t mnk_conv2d_stats_floats(int N, int Ho, int Wo, int C0, int C1, int Cout, int ntaps) {
-    if (N <= 0 || Ho <= 0 || Wo <= 0 || C0 <= 0 || C1 < 0 || Cout <= 0 || ntaps <= 0) return 0;
-    const int chunks = (round_up(C0, 16) + (C1 > 0 ? round_up(C1, 16) : 0)) / 16;
-    Plan p = make_plan((long)N * Ho * Wo, Cout, chunks, ntaps);
-    if (p.splits > 1)
-        return g_splitk_stats ? (size_t)make_rsmap((long)N * Ho * Wo, round_up(Cout, 4)).row_blocks * 2 * round_up(Cout, 4) : 0;
-    return (size_t)p.gm * 2 * round_up(Cout, 4);
+    return plan_launch(ntaps, 1, N, Ho, Wo, C0, C1, Cout).stats_floats;
 }
 
 }  // extern "C"
+
+// ---- the GEMM kernel of a plan: block tile (plan_tile_ok) x loader mode x GEMM mode --------------------------------------------
+struct IgemmLaunch {
+    dim3 grid;
+    hipStream_t s;
+    bool timed;               // the roofline kernel is timed by its own begin / end stamps
+    hipEvent_t ev0, ev1;
+};
+static void launch_igemm(void (*kernel)(ConvArgs), const IgemmLaunch& L, const ConvArgs& a) {
+    if (L.timed) hipExtLaunchKernelGGL(kernel, L.grid, dim3(256), 0, L.s, L.ev0, L.ev1, 0, a);
+    else hipLaunchKernelGGL(kernel, L.grid, dim3(256), 0, L.s, a);
+}
+// the 32x32-MFMA kernel of a tile / the 16x16-MFMA kernel of a width, by loader mode; GM: 1 = bf16x3 products
+template <int BM, int BN, int WM, int WN, int GM>
+static void launch_tile(int mode, const IgemmLaunch& L, const ConvArgs& a) {
+    if (mode == 1) launch_igemm(conv3x3_igemm_kernel<BM, BN, WM, WN, 1, GM>, L, a);
+    else if (mode == 2) launch_igemm(conv3x3_igemm_kernel<BM, BN, WM, WN, 2, GM>, L, a);
+    else if (mode == 3) launch_igemm(conv3x3_igemm_kernel<BM, BN, WM, WN, 3, GM>, L, a);
+    else launch_igemm(conv3x3_igemm_kernel<BM, BN, WM, WN, 0, GM>, L, a);
+}
+template <int BN, int GM>
+static void launch_tile16(int mode, const IgemmLaunch& L, const ConvArgs& a) {
+    if (mode == 1) launch_igemm(conv3x3_igemm16_kernel<BN, 1, GM>, L, a);
+    else if (mode == 2) launch_igemm(conv3x3_igemm16_kernel<BN, 2, GM>, L, a);
+    else if (mode == 3) launch_igemm(conv3x3_igemm16_kernel<BN, 3, GM>, L, a);
+    else launch_igemm(conv3x3_igemm16_kernel<BN, 0, GM>, L, a);
+}
+template <int GM>
+static void launch_plan_tile(const Plan& p, int mode, const IgemmLaunch& L, const ConvArgs& a) {
+    if (p.bn == 16) launch_tile16<16, GM>(mode, L, a);
+    else if (p.bn == 48) launch_tile16<48, GM>(mode, L, a);
+    else if (p.bn == 128 && p.bm == 128) launch_tile<128, 128, 2, 2, GM>(mode, L, a);
+    else if (p.bn == 128) launch_tile<64, 128, 1, 4, GM>(mode, L, a);
+    else if (p.bn == 64 && p.bm == 128) launch_tile<128, 64, 2, 2, GM>(mode, L, a);
+    else if (p.bn == 64) launch_tile<64, 64, 2, 2, GM>(mode, L, a);
+    else launch_tile<128, 32, 4, 1, GM>(mode, L, a);
+}
 
 // general form behind mnk_conv2d_fwd / mnk_conv3x3_up_fwd / mnk_conv3x3_up_dgrad:
 //   phases == 1: Ho x Wo outputs, input pixel of output (h, w), tap (ky, kx) = (h * stride + ky - pad, w * stride + kx - pad)
@@ -1613,7 +1664,8 @@ static int conv2d_fwd_impl(const float* x0, int ld0, int C0, const float* x1, in
     a.chunks = (a.C0p + a.C1p) / 16;
     a.stride = stride;
     a.pad_x = -1;
-    Plan p = make_plan(a.M, Cout, a.chunks, ntaps, phases);
+    const Launch l = plan_launch(ntaps, phases, N, Ho, Wo, C0, C1, Cout);
+    const Plan& p = l.p;
     a.phases = phases;
     a.tiles_per_phase = p.gm;
     a.phase_wstride = (long)Cout * ntaps * (a.C0p + a.C1p);
@@ -1627,9 +1679,10 @@ static int conv2d_fwd_impl(const float* x0, int ld0, int C0, const float* x1, in
     MNK_REQUIRE(!bnb || (stats_partial && bnb->y && bnb->mean && bnb->invstd && bnb->scale && bnb->beta && bnb->ld >= Cout &&
                          phases == 1 && !defer_splitk));
     a.xcd = g_xcd_remap;
-    MNK_REQUIRE(!stats_partial || (ld_y == round_up(Cout, 4) && (p.splits == 1 || (g_splitk_stats && !defer_splitk))));
-    if (p.splits > 1 && (!ws || ws_floats < (size_t)p.splits * phases * a.M * p.ldw)) {
-        set_error("mnk_conv2d_fwd: workspace too small (%zu < %zu floats)", ws_floats, (size_t)p.splits * phases * a.M * p.ldw);
+    // statistics: only where the query answers > 0, and not from partials that are left to the caller
+    MNK_REQUIRE(!stats_partial || (ld_y == round_up(Cout, 4) && l.stats_floats && (p.splits == 1 || !defer_splitk)));
+    if (l.ws_floats && (!ws || ws_floats < l.ws_floats)) {
+        set_error("mnk_conv2d_fwd: workspace too small (%zu < %zu floats)", ws_floats, l.ws_floats);
         return MNK_EWORKSPACE;
     }
     hipStream_t s = (hipStream_t)stream;
@@ -1663,63 +1716,9 @@ static int conv2d_fwd_impl(const float* x0, int ld0, int C0, const float* x1, in
         // (padding a block's LDS request so that exactly ceil(blocks / CUs) blocks fit a CU was built and measured in round 4: the
         // dispatcher already puts 1024 blocks on 256 CUs four by four -- tools/microbench/launch_gap.hip (e) -- and the step did
         // not move, 10.33 vs 10.32 ms: removed.  profiles/r04_knob_ab_log.txt)
-        const unsigned dyn = 0;
-#define MNK_IGEMM_MODE(KERNEL, MODE, ...)                                                                       \
-    do {                                                                                                        \
-        if (timed) hipExtLaunchKernelGGL((KERNEL<__VA_ARGS__, MODE>), grid, dim3(256), dyn, s, ev0, ev1, 0, a); \
-        else hipLaunchKernelGGL((KERNEL<__VA_ARGS__, MODE>), grid, dim3(256), dyn, s, a);                       \
-    } while (0)
-#define MNK_IGEMM_MODE_H(KERNEL, MODE, ...)                                                                        \
-    do {                                                                                                           \
-        if (timed) hipExtLaunchKernelGGL((KERNEL<__VA_ARGS__, MODE, 1>), grid, dim3(256), dyn, s, ev0, ev1, 0, a); \
-        else hipLaunchKernelGGL((KERNEL<__VA_ARGS__, MODE, 1>), grid, dim3(256), dyn, s, a);                       \
-    } while (0)
-#define MNK_IGEMM_H(KERNEL, ...)                                      \
-    do {                                                              \
-        if (mode == 1) MNK_IGEMM_MODE_H(KERNEL, 1, __VA_ARGS__);      \
-        else if (mode == 2) MNK_IGEMM_MODE_H(KERNEL, 2, __VA_ARGS__); \
-        else if (mode == 3) MNK_IGEMM_MODE_H(KERNEL, 3, __VA_ARGS__); \
-        else MNK_IGEMM_MODE_H(KERNEL, 0, __VA_ARGS__);                \
-    } while (0)
-#define MNK_IGEMM(KERNEL, ...)                                      \
-    do {                                                            \
-        if (mode == 1) MNK_IGEMM_MODE(KERNEL, 1, __VA_ARGS__);      \
-        else if (mode == 2) MNK_IGEMM_MODE(KERNEL, 2, __VA_ARGS__); \
-        else if (mode == 3) MNK_IGEMM_MODE(KERNEL, 3, __VA_ARGS__); \
-        else MNK_IGEMM_MODE(KERNEL, 0, __VA_ARGS__);                \
-    } while (0)
-        if (p.bn == 16 && g_gemm16_bf16x3)
-            MNK_IGEMM_H(conv3x3_igemm16_kernel, 16);
-        else if (p.bn == 48 && g_gemm16_bf16x3)
-            MNK_IGEMM_H(conv3x3_igemm16_kernel, 48);
-        else if (p.bn == 16)
-            MNK_IGEMM(conv3x3_igemm16_kernel, 16);
-        else if (p.bn == 48)
-            MNK_IGEMM(conv3x3_igemm16_kernel, 48);
-        else if (g_gemm_bf16x3 && p.bn == 128 && p.bm == 128)
-            MNK_IGEMM_H(conv3x3_igemm_kernel, 128, 128, 2, 2);
-        else if (g_gemm_bf16x3 && p.bn == 128)
-            MNK_IGEMM_H(conv3x3_igemm_kernel, 64, 128, 1, 4);
-        else if (g_gemm_bf16x3 && p.bn == 64 && p.bm == 128)
-            MNK_IGEMM_H(conv3x3_igemm_kernel, 128, 64, 2, 2);
-        else if (g_gemm_bf16x3 && p.bn == 64)
-            MNK_IGEMM_H(conv3x3_igemm_kernel, 64, 64, 2, 2);
-        else if (g_gemm_bf16x3)
-            MNK_IGEMM_H(conv3x3_igemm_kernel, 128, 32, 4, 1);
-        else if (p.bn == 128 && p.bm == 128)
-            MNK_IGEMM(conv3x3_igemm_kernel, 128, 128, 2, 2);
-        else if (p.bn == 128)
-            MNK_IGEMM(conv3x3_igemm_kernel, 64, 128, 1, 4);
-        else if (p.bn == 64 && p.bm == 128)
-            MNK_IGEMM(conv3x3_igemm_kernel, 128, 64, 2, 2);
-        else if (p.bn == 64)
-            MNK_IGEMM(conv3x3_igemm_kernel, 64, 64, 2, 2);
-        else
-            MNK_IGEMM(conv3x3_igemm_kernel, 128, 32, 4, 1);
-#undef MNK_IGEMM
-#undef MNK_IGEMM_MODE
-#undef MNK_IGEMM_H
-#undef MNK_IGEMM_MODE_H
+        const IgemmLaunch L = {grid, s, timed, ev0, ev1};
+        if (p.bn == 16 || p.bn == 48 ? g_gemm16_bf16x3 : g_gemm_bf16x3) launch_plan_tile<1>(p, mode, L, a);
+        else launch_plan_tile<0>(p, mode, L, a);
     }
     if (p.splits > 1 && !defer_splitk) {
         ProfScope prof(K_CONV_REDUCE, s, (double)p.splits * a.M * p.ldw * 4);
@@ -1790,18 +1789,10 @@ int mnk_conv3x3_up_pack_dgrad(const float* w, float* wp, int Cout, int Cin_total
     return MNK_OK;
 }
 size_t mnk_conv3x3_up_workspace_floats(int N, int H, int W, int C0, int C1, int Cout) {
-    if (N <= 0 || H <= 0 || W <= 0 || C0 <= 0 || C1 < 0 || Cout <= 0) return 0;
-    const int chunks = (round_up(C0, 16) + (C1 > 0 ? round_up(C1, 16) : 0)) / 16;
-    Plan p = make_plan((long)N * H * W, Cout, chunks, 4, 4);
-    return p.splits > 1 ? (size_t)p.splits * 4 * N * H * W * p.ldw : 0;
+    return plan_launch(4, 4, N, H, W, C0, C1, Cout).ws_floats;
 }
 size_t mnk_conv3x3_up_stats_floats(int N, int H, int W, int C0, int C1, int Cout) {
-    if (N <= 0 || H <= 0 || W <= 0 || C0 <= 0 || C1 < 0 || Cout <= 0) return 0;
-    const int chunks = (round_up(C0, 16) + (C1 > 0 ? round_up(C1, 16) : 0)) / 16;
-    Plan p = make_plan((long)N * H * W, Cout, chunks, 4, 4);
-    if (p.splits > 1)
-        return g_splitk_stats ? (size_t)make_rsmap(4L * N * H * W, round_up(Cout, 4)).row_blocks * 2 * round_up(Cout, 4) : 0;
-    return (size_t)4 * p.gm * 2 * round_up(Cout, 4);
+    return plan_launch(4, 4, N, H, W, C0, C1, Cout).stats_floats;
 }
 int mnk_conv3x3_up_fwd(const float* x0, int ld0, int C0, const float* x1, int ld1, int C1, int flags, const float* wp_up,
                        const float* bias, float* y, int ld_y, int N, int H, int W, int Cout, float* ws, size_t ws_floats,
@@ -1811,19 +1802,11 @@ int mnk_conv3x3_up_fwd(const float* x0, int ld0, int C0, const float* x1, int ld
                            ld_y, N, H, W, Cout, ws, ws_floats, stats_partial, stream);
 }
 // pixel-independent K splits of the launches above (1: no split): what a caller that sums the partials itself must know
-int mnk_conv3x3_splits(int N, int H, int W, int C0, int C1, int Cout) {
-    if (N <= 0 || H <= 0 || W <= 0 || C0 <= 0 || C1 < 0 || Cout <= 0) return 0;
-    return make_plan((long)N * H * W, Cout, (round_up(C0, 16) + (C1 > 0 ? round_up(C1, 16) : 0)) / 16, 9, 1).splits;
-}
-int mnk_conv3x3_up_splits(int N, int H, int W, int C0, int C1, int Cout) {
-    if (N <= 0 || H <= 0 || W <= 0 || C0 <= 0 || C1 < 0 || Cout <= 0) return 0;
-    return make_plan((long)N * H * W, Cout, (round_up(C0, 16) + (C1 > 0 ? round_up(C1, 16) : 0)) / 16, 4, 4).splits;
-}
+int mnk_conv3x3_splits(int N, int H, int W, int C0, int C1, int Cout) { return plan_launch(9, 1, N, H, W, C0, C1, Cout).p.splits; }
+int mnk_conv3x3_up_splits(int N, int H, int W, int C0, int C1, int Cout) { return plan_launch(4, 4, N, H, W, C0, C1, Cout).p.splits; }
 // data gradient w.r.t. one low-resolution source of an up-sampled convolution: dy (N, 2H, 2W, Cout) -> dx (N, H, W, C)
 size_t mnk_conv3x3_up_dgrad_workspace_floats(int N, int H, int W, int Cout, int C) {
-    if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || Cout <= 0) return 0;
-    Plan p = make_plan((long)N * H * W, C, round_up(Cout, 16) / 16, 16, 1);
-    return p.splits > 1 ? (size_t)p.splits * N * H * W * p.ldw : 0;
+    return plan_launch(16, 1, N, H, W, Cout, 0, C).ws_floats;
 }
 int mnk_conv3x3_up_dgrad(const float* dy, int ld_dy, int Cout, const float* wp_up_dgrad, float* dx, int ld_dx, int N, int H,
                          int W, int C, float* ws, size_t ws_floats, void* stream) {
@@ -1847,7 +1830,7 @@ int mnk_conv3x3_dgrad_bnstats(const float* dy, int ld_dy, int Cout, const float*
                            ld_res, dx, ld_dx, N, H, W, C, ws, ws_floats, stats_partial, stream, &b);
 }
 size_t mnk_conv3x3_up_dgrad_stats_floats(int N, int H, int W, int Cout, int C) {
-    return mnk_conv2d_stats_floats(N, H, W, Cout, 0, C, 16);
+    return plan_launch(16, 1, N, H, W, Cout, 0, C).stats_floats;
 }
 int mnk_conv3x3_up_dgrad_bnstats(const float* dy, int ld_dy, int Cout, const float* wp_up_dgrad, float* dx, int ld_dx, int N, int H,
                                  int W, int C, float* ws, size_t ws_floats, float* stats_partial, const float* bn_y, int ld_bny,

@@ -6,6 +6,7 @@ are zero).  The logical channel count travels next to the tensor.  PyTorch is us
 autograd tape only; every arithmetic step is a kernel launch through `mnk._lib` (no CPU / eager fallback).
 """
 import weakref
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -366,6 +367,29 @@ def subpixel(ups):
 FROZEN_CAPTURE = [False]
 
 
+# The entry points of one form of the forward / data-gradient implicit GEMM (csrc/conv3x3.hip): packed size and pack of its
+# weights, the three size queries (splits: None where the form has none), the launch, the launch that also leaves the backward
+# statistics of the BatchNorm in front (None: no such form), and the phases of a launch.
+_GemmForm = namedtuple("_GemmForm", "packed pack ws stats splits launch bn_launch phases", defaults=(None, 1))
+
+
+# the only place these names are chosen: everything below asks for a form
+_FORMS = {
+    # 3x3 / pad 1, forward and (on dy, with the data-gradient pack) data gradient
+    "3x3": _GemmForm("mnk_conv3x3_packed_floats", "mnk_conv3x3_pack_fwd", "mnk_conv3x3_workspace_floats",
+                     "mnk_conv3x3_stats_floats", "mnk_conv3x3_splits", "mnk_conv3x3_fwd", "mnk_conv3x3_dgrad_bnstats"),
+    # [nearest x2 -> 3x3 / pad 1] in its sub-pixel forms; (H, W) of their calls = the LOW resolution
+    "up": _GemmForm("mnk_conv3x3_up_packed_floats", "mnk_conv3x3_up_pack_fwd", "mnk_conv3x3_up_workspace_floats",
+                    "mnk_conv3x3_up_stats_floats", "mnk_conv3x3_up_splits", "mnk_conv3x3_up_fwd", phases=4),
+    "up_dgrad": _GemmForm("mnk_conv3x3_up_dgrad_packed_floats", "mnk_conv3x3_up_pack_dgrad",
+                          "mnk_conv3x3_up_dgrad_workspace_floats", "mnk_conv3x3_up_dgrad_stats_floats", None,
+                          "mnk_conv3x3_up_dgrad", "mnk_conv3x3_up_dgrad_bnstats"),
+    # K x K, any pad, one source (the discriminator); its data gradient is the same form on dy
+    "kxk": _GemmForm("mnk_conv2d_packed_floats", "mnk_conv2d_pack_fwd", "mnk_conv2d_workspace_floats", "mnk_conv2d_stats_floats",
+                     None, "mnk_conv2d_fwd"),
+}
+
+
 def _packed_fwd_weight(weight, cout, c0, c1, up=False):
     """Packed [Cout][chunk][tap][16] copy of a conv weight for NO-GRAD forwards (inference loops), cached per parameter
     version, storage and optimiser epoch.  Training forwards never use this cache (they take the registry entry of
@@ -373,8 +397,8 @@ def _packed_fwd_weight(weight, cout, c0, c1, up=False):
     Under hipGraph capture the cache is bypassed: the pack launch is recorded INTO the graph (its buffer lives in the
     graph's memory pool), so every replay re-packs from the live parameter -- a replay after load_state_dict / an
     in-place write can never combine old packed weights with new normalisation parameters."""
-    n = _query("mnk_conv3x3_up_packed_floats" if up else "mnk_conv3x3_packed_floats", cout, c0, c1)
-    pack = "mnk_conv3x3_up_pack_fwd" if up else "mnk_conv3x3_pack_fwd"
+    form = _FORMS["up" if up else "3x3"]
+    n, pack = _query(form.packed, cout, c0, c1), form.pack
     if weight.is_cuda and torch.cuda.is_current_stream_capturing() and not FROZEN_CAPTURE[0]:
         wp = torch.empty(n, dtype=torch.float32, device=weight.device)
         _call(pack, weight, _p(weight), _p(wp), cout, c0, c1)
@@ -408,6 +432,7 @@ def _pack_entry(weight, cout, c0, c1, need, up=False):
     (repack_registered() ran since the last optimiser step).  up: the packs of the sub-pixel forms of an up-sampled
     convolution (mnk_conv3x3_up_fwd / _up_dgrad) instead of the 3x3 layouts."""
     meta = (cout, c0, c1, bool(up))
+    form, dform = (_FORMS["up"], _FORMS["up_dgrad"]) if up else (_FORMS["3x3"], _FORMS["3x3"])
     e = _PACK_REG.get(id(weight))
     if e is not None and e.fresh(weight, meta, need):
         return e
@@ -421,8 +446,7 @@ def _pack_entry(weight, cout, c0, c1, need, up=False):
     if e is None or e.wref() is not weight or e.wptr != weight.data_ptr() or e.meta != meta:
         e = _PackEntry()
         e.wref, e.wptr, e.meta, e.wd, e.stamp = weakref.ref(weight), weight.data_ptr(), meta, [None, None], None
-        e.wp = torch.empty(_query("mnk_conv3x3_up_packed_floats" if up else "mnk_conv3x3_packed_floats", cout, c0, c1),
-                           dtype=torch.float32, device=weight.device)
+        e.wp = torch.empty(_query(form.packed, cout, c0, c1), dtype=torch.float32, device=weight.device)
         key = id(weight)
         _PACK_REG[key] = e
         weakref.finalize(weight, _drop_pack_entry, key, weakref.ref(e))
@@ -430,15 +454,15 @@ def _pack_entry(weight, cout, c0, c1, need, up=False):
         _PACK_REG_VERSION[0] += 1
     for i, cc in enumerate((c0, c1)):
         if need[i] and e.wd[i] is None:
-            nd = _query("mnk_conv3x3_up_dgrad_packed_floats", cout, cc) if up else _query("mnk_conv3x3_packed_floats", cc, cout, 0)
+            nd = _query(dform.packed, cout, cc) if up else _query(dform.packed, cc, cout, 0)
             e.wd[i] = torch.empty(nd, dtype=torch.float32, device=weight.device)
             _PACK_TABLE["dirty"] = True
             _PACK_REG_VERSION[0] += 1
     if up:
-        _call("mnk_conv3x3_up_pack_fwd", weight, _p(weight), _p(e.wp), cout, c0, c1)
+        _call(form.pack, weight, _p(weight), _p(e.wp), cout, c0, c1)
         for i, (cs, cc) in enumerate(((0, c0), (c0, c1))):
             if e.wd[i] is not None:
-                _call("mnk_conv3x3_up_pack_dgrad", weight, _p(weight), _p(e.wd[i]), cout, c0 + c1, cs, cc)
+                _call(dform.pack, weight, _p(weight), _p(e.wd[i]), cout, c0 + c1, cs, cc)
     else:
         _call("mnk_conv3x3_pack_all", weight, _p(weight), _p(e.wp), _p(e.wd[0]), _p(e.wd[1]), cout, c0, c1)
     e.stamp = None            # only repack_registered() vouches for freshness: a user-owned loop packs on every call
@@ -496,9 +520,13 @@ def repack_registered(only_if_stale=False):
     return True
 
 
-# a split-K convolution whose partials a small-layer BatchNorm will sum: y.data_ptr() -> (ws, splits, phases, bias)
+# a split-K convolution whose partials a small-layer BatchNorm will sum: y.data_ptr() -> _SplitPending
 _SPLIT_PENDING = {}
-_EVAL_DEFER = [False]                     # conv3x3(eval_bn=True) -> _conv_launch
+
+
+# the partials of a deferred split-K launch: [splits][phases][M][ld] floats at `ws`, the bias not added
+_SplitPending = namedtuple("_SplitPending", "ws splits phases bias")
+_NO_SPLIT = _SplitPending(None, 0, 1, None)      # what a BatchNorm with nothing pending tells its kernel
 
 
 def _small_sync(rows):
@@ -515,18 +543,15 @@ def small_bn(rows, training=True, c=0):
     return not mdist.active() or _sync_handle(c) is not None
 
 
-def _conv_launch(x0, c0, x1, c1, ups, wp, bias, residual, n, h, w, cout, want_stats=False, up=False):
-    """One conv launch.  With want_stats the BatchNorm sums of the output come out of the conv epilogue (finished by a
-    tiny second-stage kernel) instead of a separate pass over y; returns (y, sums or None).  up: `wp` holds the
-    sub-pixel packs of an up-sampled convolution and (h, w) is the up-sampled size."""
-    y = torch.empty(n, h, w, ceil4(cout), dtype=torch.float32, device=x0.device)
-    # a small layer whose BatchNorm follows at once (want_stats): that one-launch kernel makes its own statistics and,
-    # when this convolution is split along K, also sums the partials -- no separate reduction, no epilogue statistics
-    # (even sizes only: a pooling BatchNorm on an odd map -- 96 x 96 frames reach 3 x 3 -- takes the general kernels, and this
-    # function does not know whether the BatchNorm that follows pools)
-    small = want_stats and residual is None and small_bn(n * h * w, True, cout) and h % 2 == 0 and w % 2 == 0
-    # evaluation mode, conv3x3(eval_bn=True): the norm layer that follows sums a split launch's partials itself (one-shot flag)
-    evald, _EVAL_DEFER[0] = (_EVAL_DEFER[0] and not want_stats and residual is None and h % 2 == 0 and w % 2 == 0), False
+def _gemm_launch(form, x0, c0, x1, c1, wp, bias, residual, n, h, w, cout, flags=0, stats=False, defer=False, bn=None, kxk=None):
+    """One forward / data-gradient GEMM launch of `form` (_FORMS): sizes its workspace (and, with `stats`, its statistics buffer)
+    by the form's queries, takes the scratch workspace and launches.  -> (y, statistics partials or None).
+    (n, h, w): the map of the form's calls -- the LOW resolution for "up" (y is twice as large) and "up_dgrad"; a data gradient
+    reads dy as x0 (c0 = its channels) and writes cout = the source's channels.
+    defer: a launch that splits along K leaves its partials in the workspace for the BatchNorm that follows (_SPLIT_PENDING).
+    bn: the _BnRecord of the BatchNorm in front of a data gradient, whose backward statistics the launch leaves where its plan
+    has a statistics form (else an ordinary launch).  kxk: (hi, wi, kh, kw, pad) of the "kxk" form."""
+    f = _FORMS[form]
     if _SPLIT_PENDING:
         # the BatchNorm of an earlier deferred split-K convolution never ran: an exception between the two launches (the entry
         # is popped by that BatchNorm; nothing else may run in between).  The partial sums are gone with the scratch buffer;
@@ -535,35 +560,61 @@ def _conv_launch(x0, c0, x1, c1, ups, wp, bias, residual, n, h, w, cout, want_st
         warnings.warn("dropping the deferred split-K partial sums of %d convolution(s) whose BatchNorm never ran (an "
                       "exception between a convolution and its normalisation layer?)" % len(_SPLIT_PENDING))
         _SPLIT_PENDING.clear()
-    if up:
-        assert ups and residual is None
-        hl, wl = h // 2, w // 2
-        nws = _query("mnk_conv3x3_up_workspace_floats", n, hl, wl, c0, c1, cout)
-        ws = SCRATCH.get("ws", nws, x0) if nws else None
-        nst = _query("mnk_conv3x3_up_stats_floats", n, hl, wl, c0, c1, cout) if want_stats and not small else 0
-        st = torch.empty(nst, dtype=torch.float32, device=x0.device) if nst else None
-        defer = 4 if (small or evald) and nws else 0
-        _call("mnk_conv3x3_up_fwd", x0, _p(x0), x0.shape[-1], c0, _p(x1), x1.shape[-1] if x1 is not None else 0, c1, defer,
-              _p(wp), _p(bias), _p(y), y.shape[-1], n, hl, wl, cout, _p(ws), nws, _p(st))
-        if defer:
-            _SPLIT_PENDING[y.data_ptr()] = (ws, _query("mnk_conv3x3_up_splits", n, hl, wl, c0, c1, cout), 4, bias)
+    up = form == "up"
+    y = torch.empty(n, h * 2 if up else h, w * 2 if up else w, ceil4(cout), dtype=torch.float32, device=x0.device)
+    size = (n, h, w, c0, cout) if form == "up_dgrad" else (n, h, w, c0, c1, cout, kxk[2] * kxk[3]) if kxk else (n, h, w, c0, c1, cout)
+    nws = _query(f.ws, *size)
+    ws = SCRATCH.get("ws", nws, x0) if nws else None
+    nst = _query(f.stats, *size) if stats or bn is not None else 0
+    st = torch.empty(nst, dtype=torch.float32, device=x0.device) if nst else None      # lives until the norm layer reads it
+    deferred = defer and nws
+    if deferred:
+        flags |= 4                       # MNK_CONV_DEFER_SPLITK
+    # (plain positional calls: this is the host-bound evaluation loops' path)
+    ld1, ldr = x1.shape[-1] if x1 is not None else 0, residual.shape[-1] if residual is not None else 0
+    if bn is not None and st is not None:
+        tail = (_p(ws), nws, _p(st), _p(bn.y), bn.y.shape[-1], _p(bn.mean), _p(bn.invstd), _p(bn.scale), _p(bn.beta), float(bn.slope))
+        if form == "3x3":
+            _call(f.bn_launch, x0, _p(x0), x0.shape[-1], c0, _p(wp), _p(residual), ldr, _p(y), y.shape[-1], n, h, w, cout, *tail)
+        else:
+            _call(f.bn_launch, x0, _p(x0), x0.shape[-1], c0, _p(wp), _p(y), y.shape[-1], n, h, w, cout, *tail)
+    elif form == "3x3":
+        _call(f.launch, x0, _p(x0), x0.shape[-1], c0, _p(x1), ld1, c1, flags, _p(wp), _p(bias), _p(residual), ldr, _p(y), y.shape[-1],
+              n, h, w, cout, _p(ws), nws, _p(st))
+    elif up:
+        _call(f.launch, x0, _p(x0), x0.shape[-1], c0, _p(x1), ld1, c1, flags, _p(wp), _p(bias), _p(y), y.shape[-1], n, h, w, cout,
+              _p(ws), nws, _p(st))
+    elif form == "up_dgrad":
+        _call(f.launch, x0, _p(x0), x0.shape[-1], c0, _p(wp), _p(y), y.shape[-1], n, h, w, cout, _p(ws), nws)
     else:
-        nws = _query("mnk_conv3x3_workspace_floats", n, h, w, c0, c1, cout)
-        ws = SCRATCH.get("ws", nws, x0) if nws else None
-        nst = _query("mnk_conv3x3_stats_floats", n, h, w, c0, c1, cout) if want_stats and not small else 0
-        st = torch.empty(nst, dtype=torch.float32, device=x0.device) if nst else None   # lives until the norm layer reads it
-        defer = 4 if (small or evald) and nws else 0
-        # flags: bit 0 = nearest x2 up-sampled view, bit 1 = MNK_CONV_CLEAN_PADS -- every act this module produces has zero
-        # pad channels (tests/test_modules.py::test_pad_channels_are_written pins that), so the fast 3x3 loader applies
-        _call("mnk_conv3x3_fwd", x0, _p(x0), x0.shape[-1], c0, _p(x1), x1.shape[-1] if x1 is not None else 0, c1,
-              int(ups) | 2 | defer, _p(wp), _p(bias), _p(residual), residual.shape[-1] if residual is not None else 0, _p(y),
+        _call(f.launch, x0, _p(x0), x0.shape[-1], c0, _p(x1), ld1, c1, flags, *kxk, _p(wp), _p(bias), _p(residual), ldr, _p(y),
               y.shape[-1], n, h, w, cout, _p(ws), nws, _p(st))
-        if defer:
-            _SPLIT_PENDING[y.data_ptr()] = (ws, _query("mnk_conv3x3_splits", n, h, w, c0, c1, cout), 1, bias)
+    if deferred:
+        _SPLIT_PENDING[y.data_ptr()] = _SplitPending(ws, _query(f.splits, *size), f.phases, bias)
+    return y, st
+
+
+def _conv_launch(x0, c0, x1, c1, ups, wp, bias, residual, n, h, w, cout, want_stats=False, up=False, eval_defer=False):
+    """One conv launch.  With want_stats the BatchNorm sums of the output come out of the conv epilogue (finished by a
+    tiny second-stage kernel) instead of a separate pass over y; returns (y, sums or None).  up: `wp` holds the
+    sub-pixel packs of an up-sampled convolution and (h, w) is the up-sampled size.  eval_defer: conv3x3(eval_bn=True)."""
+    # a small layer whose BatchNorm follows at once (want_stats): that one-launch kernel makes its own statistics and,
+    # when this convolution is split along K, also sums the partials -- no separate reduction, no epilogue statistics
+    # (even sizes only: a pooling BatchNorm on an odd map -- 96 x 96 frames reach 3 x 3 -- takes the general kernels, and this
+    # function does not know whether the BatchNorm that follows pools)
+    small = want_stats and residual is None and small_bn(n * h * w, True, cout) and h % 2 == 0 and w % 2 == 0
+    # evaluation mode: the norm layer that follows sums a split launch's partials itself
+    evald = eval_defer and not want_stats and residual is None and h % 2 == 0 and w % 2 == 0
+    assert not up or (ups and residual is None)
+    # flags: bit 0 = nearest x2 up-sampled view, bit 1 = MNK_CONV_CLEAN_PADS -- every act this module produces has zero
+    # pad channels (tests/test_modules.py::test_pad_channels_are_written pins that), so the fast 3x3 loader applies
+    form, hq, wq, flags = ("up", h // 2, w // 2, 0) if up else ("3x3", h, w, int(ups) | 2)
+    y, st = _gemm_launch(form, x0, c0, x1, c1, wp, bias, residual, n, hq, wq, cout, flags, want_stats and not small, small or evald)
     if small:
         return y, y.new_empty(0)
     sums = None
     if want_stats:
+        nst = st.numel() if st is not None else 0
         if nst and not mdist.active():
             sums = st                          # per-block partials: finished together with the finalisation (bn_act)
         elif nst:
@@ -680,8 +731,6 @@ def handover_state():
     _DZ_STATS: entries die with their tensors or at clear_dz_stats().)"""
     slots = {
         "_SPLIT_PENDING (split-K convolution -> the norm layer that sums its partials)": len(_SPLIT_PENDING),
-        "_EVAL_DEFER (conv3x3(eval_bn=True) -> _conv_launch)": _EVAL_DEFER[0],
-        "_SRC_BN (conv3x3 -> Conv3x3Fn.forward)": _SRC_BN[0],
         "_LAST_BN (BNActFn.forward -> bn_act)": _LAST_BN[0],
         "_DY_SUMS (BNActFn.backward -> Conv3x3Fn.backward)": _DY_SUMS[0],
         "_SKIP_PARAM_GRADS (no_param_grads)": _SKIP_PARAM_GRADS[0],
@@ -691,15 +740,14 @@ def handover_state():
     return {k: v for k, v in slots.items() if v}
 
 
-_SRC_BN = [None]                          # conv3x3() -> Conv3x3Fn.forward: (record of x0's norm layer or None, of x1's)
-
-
 class Conv3x3Fn(_Fn):
     """nn.Conv3d((1,3,3), padding (0,1,1)) over the channel concatenation [x0 | x1], optionally read through the
     nearest x2 up-sampling (UpBlock3D, modules/util.py:83-85), plus bias and residual add (ResBlock3D :66-67)."""
 
     @staticmethod
-    def forward(ctx, x0, x1, weight, bias, residual, c0, c1, ups, want_stats, track):
+    def forward(ctx, x0, x1, weight, bias, residual, c0, c1, ups, want_stats, track, src_bn=None, eval_defer=False):
+        """src_bn: (the _BnRecord of the norm layer whose output x0 is, or None; the same for x1), see _BN_OF.
+        eval_defer: conv3x3(eval_bn=True), see _conv_launch."""
         _check_device(x0)
         cout = weight.shape[0]
         assert weight.shape[1] == c0 + c1 and weight.is_contiguous()
@@ -714,9 +762,9 @@ class Conv3x3Fn(_Fn):
             wp, ctx.wd = e.wp, list(e.wd)
         else:
             wp = _packed_fwd_weight(weight, cout, c0, c1, up)
-        y, sums = _conv_launch(x0, c0, x1, c1, ups, wp, bias, residual, n, h, w, cout, want_stats, up)
+        y, sums = _conv_launch(x0, c0, x1, c1, ups, wp, bias, residual, n, h, w, cout, want_stats, up, eval_defer)
         ctx.up = up
-        ctx.src_bn, _SRC_BN[0] = (_SRC_BN[0] if track and _SRC_BN[0] is not None else (None, None)), None
+        ctx.src_bn = src_bn if track and src_bn is not None else (None, None)
         ctx.save_for_backward(x0, x1, weight)
         ctx.meta = (c0, c1, ups, cout, n, h, w, bias is not None, residual is not None)
         if sums is None:
@@ -735,7 +783,7 @@ class Conv3x3Fn(_Fn):
         x0, x1, weight = ctx.saved_tensors
         c0, c1, ups, cout, n, h, w, has_bias, has_res = ctx.meta
         if dy is None:                       # (materialize_grads is off) nothing flows into y
-            return (dskip if ctx.needs_input_grad[0] else None,) + (None,) * 9
+            return (dskip if ctx.needs_input_grad[0] else None,) + (None,) * 11
         if dskip is not None and not ctx.needs_input_grad[0]:
             dskip = None
         dy_in = dy
@@ -753,45 +801,25 @@ class Conv3x3Fn(_Fn):
             if rec is not None and (rec.c != cc or rec.y.shape[-1] != ceil4(cc) or small_bn(rec.y.numel() // rec.y.shape[-1], True, cc)
                                     or _small_sync(rec.y.numel() // rec.y.shape[-1])):
                 rec = None               # (small layers make their backward statistics inside their own one-launch kernel)
+            res = None
             if ctx.up:
                 # data gradient w.r.t. the low-resolution source: one 4x4 / stride 2 convolution over dy (no gradient of
                 # the up-sampled view, no 2x2 sum-pool pass)
-                dx = torch.empty(n, h // 2, w // 2, ceil4(cc), dtype=torch.float32, device=dy.device)
-                nws = _query("mnk_conv3x3_up_dgrad_workspace_floats", n, h // 2, w // 2, cout, cc)
-                ws = SCRATCH.get("ws", nws, dy) if nws else None
-                nst = _query("mnk_conv3x3_up_dgrad_stats_floats", n, h // 2, w // 2, cout, cc) if (
-                    rec is not None and tuple(rec.y.shape) == tuple(dx.shape)) else 0
-                if nst:
-                    st = torch.empty(nst, dtype=torch.float32, device=dy.device)
-                    _call("mnk_conv3x3_up_dgrad_bnstats", dy, _p(dy), ld_dy, cout, _p(wp), _p(dx), dx.shape[-1], n, h // 2,
-                          w // 2, cc, _p(ws), nws, _p(st), _p(rec.y), rec.y.shape[-1], _p(rec.mean), _p(rec.invstd),
-                          _p(rec.scale), _p(rec.beta), float(rec.slope))
-                    _DZ_STATS[dx.data_ptr()] = (dx, st, nst // (2 * dx.shape[-1]), rec.y.data_ptr())
-                else:
-                    _call("mnk_conv3x3_up_dgrad", dy, _p(dy), ld_dy, cout, _p(wp), _p(dx), dx.shape[-1], n, h // 2, w // 2, cc,
-                          _p(ws), nws)
-                grads[i] = dx
-                continue
-            # x0's second gradient rides as the residual operand of the data-gradient GEMM (its epilogue / split reduction)
-            res = None
-            if i == 0 and dskip is not None and not ups:
-                res, dskip = dskip.contiguous(), None
-                assert res.shape == (n, h, w, ceil4(cc))
-            nst = _query("mnk_conv3x3_stats_floats", n, h, w, cout, 0, cc) if (
-                rec is not None and not ups and tuple(rec.y.shape) == (n, h, w, ceil4(cc))) else 0
-            if nst:
-                dx = torch.empty(n, h, w, ceil4(cc), dtype=torch.float32, device=dy.device)
-                nws = _query("mnk_conv3x3_workspace_floats", n, h, w, cout, 0, cc)
-                ws = SCRATCH.get("ws", nws, dy) if nws else None
-                st = torch.empty(nst, dtype=torch.float32, device=dy.device)
-                _call("mnk_conv3x3_dgrad_bnstats", dy, _p(dy), ld_dy, cout, _p(wp), _p(res),
-                      res.shape[-1] if res is not None else 0, _p(dx), dx.shape[-1], n, h, w, cc, _p(ws), nws, _p(st), _p(rec.y),
-                      rec.y.shape[-1], _p(rec.mean), _p(rec.invstd), _p(rec.scale), _p(rec.beta), float(rec.slope))
-                _DZ_STATS[dx.data_ptr()] = (dx, st, nst // (2 * dx.shape[-1]), rec.y.data_ptr())
-                grads[i] = dx
-                continue
-            dx, _ = _conv_launch(dy, cout, None, 0, 0, wp, None, res, n, h, w, cc)
-            if ups:
+                form, hd, wd = "up_dgrad", h // 2, w // 2
+            else:
+                form, hd, wd = "3x3", h, w
+                # x0's second gradient rides as the residual operand of the data-gradient GEMM (its epilogue / split reduction)
+                if i == 0 and dskip is not None and not ups:
+                    res, dskip = dskip.contiguous(), None
+                    assert res.shape == (n, h, w, ceil4(cc))
+                if ups:
+                    rec = None
+            if rec is not None and tuple(rec.y.shape) != (n, hd, wd, ceil4(cc)):
+                rec = None
+            dx, st = _gemm_launch(form, dy, cout, None, 0, wp, None, res, n, hd, wd, cc, 2, bn=rec)
+            if rec is not None and st is not None:
+                _DZ_STATS[dx.data_ptr()] = (dx, st, st.numel() // (2 * dx.shape[-1]), rec.y.data_ptr())
+            if ups and not ctx.up:
                 dxs = torch.empty(n, h // 2, w // 2, ceil4(cc), dtype=torch.float32, device=dy.device)
                 _call("mnk_sumpool2x2", dy, _p(dx), dx.shape[-1], _p(dxs), dxs.shape[-1], n, h, w, cc)
                 dx = dxs
@@ -832,7 +860,7 @@ class Conv3x3Fn(_Fn):
         dres = dy if has_res and ctx.needs_input_grad[4] else None
         if dskip is not None:                # forms without a residual operand (up-sampled sources): one add
             grads[0] = grads[0] + dskip if grads[0] is not None else dskip
-        return grads[0], grads[1], dw, db, dres, None, None, None, None, None
+        return grads[0], grads[1], dw, db, dres, None, None, None, None, None, None, None
 
 
 class Conv3x3SkipFn(_Fn):
@@ -842,8 +870,8 @@ class Conv3x3SkipFn(_Fn):
     gradient in the epilogue of its data-gradient GEMM (the `residual` operand) -- no accumulation pass by autograd."""
 
     @staticmethod
-    def forward(ctx, x0, x1, weight, bias, residual, c0, c1, ups, want_stats, track):
-        y, sums = Conv3x3Fn.forward(ctx, x0, x1, weight, bias, residual, c0, c1, ups, want_stats, track)
+    def forward(ctx, x0, x1, weight, bias, residual, c0, c1, ups, want_stats, track, src_bn=None, eval_defer=False):
+        y, sums = Conv3x3Fn.forward(ctx, x0, x1, weight, bias, residual, c0, c1, ups, want_stats, track, src_bn, eval_defer)
         return y, sums, x0
 
     @staticmethod
@@ -859,20 +887,14 @@ def conv3x3(x0, c0, weight, bias=None, x1=None, c1=0, ups=False, residual=None, 
     and y is never written."""
     track = torch.is_grad_enabled() and any(
         t is not None and t.requires_grad for t in (x0, x1, weight, bias, residual))
-    _EVAL_DEFER[0] = bool(eval_bn and not want_stats and residual is None and not torch.is_grad_enabled()
-                          and knobs.form("EVAL_SPLIT_FUSED"))
-    if track:       # the norm layers whose outputs the sources are (see _BN_OF): picked up by Conv3x3Fn.forward
-        _SRC_BN[0] = (_bn_of(x0), _bn_of(x1))
-    try:
-        if skip and track and x0.requires_grad and knobs.form("SKIP_GRAD_FUSED"):
-            y, sums, through = Conv3x3SkipFn.apply(x0, x1, weight, bias, residual, c0, c1, bool(ups), bool(want_stats), track)
-            return y, (sums if want_stats else None), through
-        y, sums = Conv3x3Fn.apply(x0, x1, weight, bias, residual, c0, c1, bool(ups), bool(want_stats), track)
-    finally:
-        # one-shot hand-overs of THIS call: an exception in front of their consumer must not leave them for an unrelated launch
-        # (a data-gradient launch of a later backward also goes through _conv_launch)
-        _EVAL_DEFER[0] = False
-        _SRC_BN[0] = None
+    eval_defer = bool(eval_bn and not want_stats and residual is None and not torch.is_grad_enabled()
+                      and knobs.form("EVAL_SPLIT_FUSED"))
+    src_bn = (_bn_of(x0), _bn_of(x1)) if track else None     # the norm layers whose outputs the sources are (see _BN_OF)
+    args = (x0, x1, weight, bias, residual, c0, c1, bool(ups), bool(want_stats), track, src_bn, eval_defer)
+    if skip and track and x0.requires_grad and knobs.form("SKIP_GRAD_FUSED"):
+        y, sums, through = Conv3x3SkipFn.apply(*args)
+        return y, (sums if want_stats else None), through
+    y, sums = Conv3x3Fn.apply(*args)
     return (y, (sums if want_stats else None), x0) if skip else (y, (sums if want_stats else None))
 
 
@@ -933,14 +955,14 @@ class BNActFn(_Fn):
             # the exchange of the sums inside the launch, statistics over the rows of ALL ranks)
             ho, wo = (h // 2, w // 2) if pool else (h, w)
             z = torch.empty(n, ho, wo, ceil4(c), dtype=torch.float32, device=dev)
-            ws_, splits, phases, bias = pending if pending is not None else (None, 0, 1, None)
+            sp = pending if pending is not None else _NO_SPLIT
             if mdist.active():
                 count *= mdist.world_size()
-                _call("mnk_bn_small_fwd_sync", y, _sync_handle(c), _p(ws_), splits, ld, phases, _p(bias), _p(y), ld, n, h, w, c,
+                _call("mnk_bn_small_fwd_sync", y, _sync_handle(c), _p(sp.ws), sp.splits, ld, sp.phases, _p(sp.bias), _p(y), ld, n, h, w, c,
                       _p(gamma), _p(beta), _p(running_mean), _p(running_var), float(momentum), float(eps), _p(mean), _p(invstd),
                       _p(scale), _p(z), z.shape[-1], int(relu), int(pool), mdist.P2P_TIMEOUT_MS)
             else:
-                _call("mnk_bn_small_fwd", y, _p(ws_), splits, ld, phases, _p(bias), _p(y), ld, n, h, w, c, _p(gamma), _p(beta),
+                _call("mnk_bn_small_fwd", y, _p(sp.ws), sp.splits, ld, sp.phases, _p(sp.bias), _p(y), ld, n, h, w, c, _p(gamma), _p(beta),
                       _p(running_mean), _p(running_var), float(momentum), float(eps), _p(mean), _p(invstd), _p(scale), _p(z),
                       z.shape[-1], int(relu), int(pool))
             ctx.save_for_backward(y, mean, invstd, scale, beta)
@@ -951,10 +973,9 @@ class BNActFn(_Fn):
             # evaluation mode behind a split-K convolution (conv3x3(eval_bn=True), no_grad): reduction + affine + ReLU + pool in
             # one launch; y was never written and nothing is saved for a backward pass
             mean, invstd, scale = _bn_eval_coeffs(y, gamma, running_mean, running_var, eps, c)
-            ws_, splits, phases, bias = pending
             ho, wo = (h // 2, w // 2) if pool else (h, w)
             z = torch.empty(n, ho, wo, ceil4(c), dtype=torch.float32, device=dev)
-            _call("mnk_bn_eval_split_fwd", y, _p(ws_), splits, ld, phases, _p(bias), _p(mean), _p(scale), _p(beta), _p(z),
+            _call("mnk_bn_eval_split_fwd", y, _p(pending.ws), pending.splits, ld, pending.phases, _p(pending.bias), _p(mean), _p(scale), _p(beta), _p(z),
                   z.shape[-1], n, h, w, c, int(relu), int(pool))
             return z
         if pending is not None:
@@ -1175,21 +1196,18 @@ class ConvKxKFn(_Fn):
         n, hi, wi, ld = x.shape
         ho, wo = hi + 2 * pad - kh + 1, wi + 2 * pad - kw + 1
         nt = kh * kw
-        wp = SCRATCH.get("pack", _query("mnk_conv2d_packed_floats", cout, cin, 0, nt), x)
+        form = _FORMS["kxk"]
+        wp = SCRATCH.get("pack", _query(form.packed, cout, cin, 0, nt), x)
         ctx.wd = None
         if ctx.needs_input_grad[0] and nt <= 16:
             # forward and data-gradient layouts in ONE launch; the latter serves every backward pass through this node (the
             # generator pass and the discriminator pass of one iteration read the same, not yet updated, weights)
-            ctx.wd = torch.empty(_query("mnk_conv2d_packed_floats", cin, cout, 0, nt), dtype=torch.float32, device=x.device)
+            ctx.wd = torch.empty(_query(form.packed, cin, cout, 0, nt), dtype=torch.float32, device=x.device)
             _call("mnk_conv2d_pack_all", x, _p(weight), _p(wp), _p(ctx.wd), None, cout, cin, 0, nt)
         else:
-            _call("mnk_conv2d_pack_fwd", x, _p(weight), _p(wp), cout, cin, 0, nt)
-        y = torch.empty(n, ho, wo, ceil4(cout), dtype=torch.float32, device=x.device)
-        nws = _query("mnk_conv2d_workspace_floats", n, ho, wo, cin, 0, cout, nt)
-        ws = SCRATCH.get("ws", nws, x) if nws else None
+            _call(form.pack, x, _p(weight), _p(wp), cout, cin, 0, nt)
         # flags = MNK_CONV_CLEAN_PADS: x is an act of this module (zero pad channels) -> the K x K buffer-load loader
-        _call("mnk_conv2d_fwd", x, _p(x), ld, cin, None, 0, 0, 2, hi, wi, kh, kw, pad, _p(wp), _p(bias), None, 0, _p(y),
-              y.shape[-1], n, ho, wo, cout, _p(ws), nws, None)
+        y, _ = _gemm_launch("kxk", x, cin, None, 0, wp, bias, None, n, ho, wo, cout, 2, kxk=(hi, wi, kh, kw, pad))
         ctx.save_for_backward(x, weight)
         ctx.meta = (cin, cout, kh, kw, pad, n, hi, wi, ho, wo, bias is not None)
         return y
@@ -1204,13 +1222,9 @@ class ConvKxKFn(_Fn):
         if ctx.needs_input_grad[0] and not (ctx.leaf_input and _SKIP_LEAF_INPUT_GRADS[0]):
             wp = ctx.wd
             if wp is None:
-                wp = SCRATCH.get("pack", _query("mnk_conv2d_packed_floats", cin, cout, 0, nt), dy)
+                wp = SCRATCH.get("pack", _query(_FORMS["kxk"].packed, cin, cout, 0, nt), dy)
                 _call("mnk_conv2d_pack_dgrad", dy, _p(weight), _p(wp), cout, cin, 0, cin, nt)
-            dx = torch.empty(n, hi, wi, ceil4(cin), dtype=torch.float32, device=dy.device)
-            nws = _query("mnk_conv2d_workspace_floats", n, hi, wi, cout, 0, cin, nt)
-            ws = SCRATCH.get("ws", nws, dy) if nws else None
-            _call("mnk_conv2d_fwd", dy, _p(dy), dy.shape[-1], cout, None, 0, 0, 2, ho, wo, kh, kw, kh - 1 - pad, _p(wp), None,
-                  None, 0, _p(dx), dx.shape[-1], n, hi, wi, cin, _p(ws), nws, None)
+            dx, _ = _gemm_launch("kxk", dy, cout, None, 0, wp, None, None, n, hi, wi, cin, 2, kxk=(ho, wo, kh, kw, kh - 1 - pad))
         if ctx.needs_input_grad[1] and not _SKIP_PARAM_GRADS[0]:
             owner = wgrad_sink_owner(weight)
             if owner is None or not owner.reducer.wgrad(weight, x, x.shape[-1], cin, 0, hi, wi, kh, kw, pad, dy,
