@@ -718,6 +718,39 @@ typedef struct MnkAugJob {
 int mnk_frames_augment(const unsigned char* pool, const MnkAugJob* jobs_device, int njobs, int any_rotation, double* rot_range,
                        int any_contrast, int* contrast_mean, int H, int W, int Cout, float* out, void* stream);
 
+/* ---- device-side output path: the reference's Visualizer and its evaluation PNG strips ------------------------------------
+ * mnk_vis_grid replaces logger.py:97-126 + the uint8 conversion of :151 / :174 (Visualizer.draw_video_with_kp,
+ * create_video_column[_with_kp], create_image_grid and `(255 * image).astype(np.uint8)`), which the reference runs on the host
+ * in numpy after copying every fp32 video over PCIe: ONE launch writes the uint8 grid
+ *   out[f][b * H + h][col * W + w][ch],  f < d, b < B, col < ncol   (videos stacked along rows, columns along the width).
+ * `cols` is a HOST array of ncol <= 8 columns; it travels in the kernel arguments (no device table, capturable).  A column is a
+ * (B, 3, D, H, W) fp32 video given by its base pointer and batch / channel / frame strides in floats (the H x W planes are
+ * contiguous); frame_stride 0 is the reference's `.repeat(1, 1, d, 1, 1)` of a one-frame tensor (logger.py:132-135, :161)
+ * without the copy.  kp (may be NULL: a column without key points) = (B, d | 1, K, 2) fp32 means in [-1, 1] with its own batch /
+ * frame strides (kp_frame_stride 0: the repeated source key points of logger.py:138, :140, :164).
+ * Per pixel, bit for bit what numpy and scikit-image 0.14 compute: centre = size * (float32(kp + 1)) / 2 in float64
+ * (logger.py:99-100); key point k covers (y, x) when, with ul = max(ceil(centre - r), 0) and lr = min(floor(centre + r), size - 1)
+ * per axis, ul <= (y, x) <= lr and ((y - ul_r - (c_r - ul_r)) / r)^2 + ((x - ul_c - (c_c - ul_c)) / r)^2 < 1 in float64
+ * (skimage.draw.circle -> ellipse -> _ellipse_in_shape); the highest covering k wins (painted in ascending order, logger.py:103-105)
+ * and the pixel becomes colors[k][0..2] (K x 3 fp32, DEVICE pointer: float32(colormap(k / K)[:3])); with draw_border rows and
+ * columns 0 and -1 of every frame become 1.0 afterwards (logger.py:113-116); byte = (uint8)(float32(255) * value), truncated.
+ * Values outside [0, 256 / 255) have no defined byte in the reference (a float -> uint8 cast out of range); here they wrap
+ * through int32.  r = kp_size > 0.  K <= 32 (K may be 0 when no column has key points; colors may then be NULL). */
+typedef struct MnkVisColumn {
+    const float* video;
+    const float* kp;
+    long long batch_stride, chan_stride, frame_stride;      /* floats */
+    long long kp_batch_stride, kp_frame_stride;             /* floats */
+} MnkVisColumn;
+int mnk_vis_grid(const MnkVisColumn* cols, int ncol, int B, int C, int d, int H, int W, int K, double kp_size, int draw_border,
+                 const float* colors, uint8_t* out, void* stream);
+/* The PNG strip of the evaluation loops (reconstruction.py:66-68, prediction.py:137-139:
+ * `np.concatenate(np.transpose(video, [0, 2, 3, 4, 1])[0], axis=1)`, `(255 * strip).astype(np.uint8)`): one (C = 3, D, H, W) fp32
+ * video given by its channel / frame strides in floats -> out uint8 [H][D * W][3], the layout frames_dataset.py:14-29 reads
+ * back (and the uint8 pool of mnk_frames_gather holds). */
+int mnk_frames_to_strip(const float* video, int C, long chan_stride, long frame_stride, int D, int H, int W, uint8_t* out,
+                        void* stream);
+
 /* ---- GRU key-point predictor (modules/prediction_module.py:14-17 nn.GRU(batch_first=True) + nn.Linear; trained by
  * prediction.py:97-107, rolled out by prediction.py:116-132) -------------------------------------------------------------
  * PyTorch GRU semantics, gate order (r, z, n), weights as nn.GRU keeps them (W_ih [3H, I], W_hh [3H, H], no repacking).

@@ -39,6 +39,9 @@ KNOBS = {
     "MNK_NATIVE_PREDICTION": ("0", "1: `import modules.prediction_module` (prediction.py:10) resolves to mnk.predictor, the key-point "
                                    "GRU on the library's kernels, ahead of the reference's own modules/prediction_module.py; 0: the "
                                    "reference's file, found behind this package on sys.path"),
+    "MNK_NATIVE_VISUALIZER": ("0", "1: run_reference.py rebinds `logger.Visualizer` of the script's own logger.py (train.py's Logger, "
+                                   "reconstruction.py:70, transfer.py, prediction.py:141) to mnk.visualizer.Visualizer, which draws the "
+                                   "uint8 grids on the device in one launch; 0: the reference's numpy / skimage class"),
     "MNK_GRAD_OVERLAP": ("1", "MnkAdam: the generator-side gradient exchange runs next to the discriminator backward when there is "
                               "more than one rank (force: also on one rank); GradAverager: a bucket's all-reduce starts when its "
                               "last gradient is written; 0: in-order exchanges"),

@@ -1579,6 +1579,73 @@ def kp_pixel_index(mean, size):
     return out
 
 
+# MnkVisColumn of include/monkeynet_hip.h: two pointers and five strides, 8 bytes each
+VIS_COLUMN = np.dtype([("video", "<u8"), ("kp", "<u8"), ("batch_stride", "<i8"), ("chan_stride", "<i8"), ("frame_stride", "<i8"),
+                       ("kp_batch_stride", "<i8"), ("kp_frame_stride", "<i8")])
+
+
+def vis_grid(columns, d, kp_size, draw_border, colors, out=None):
+    """The uint8 image grid of the reference's Visualizer.create_image_grid (logger.py:97-126, :151) in one launch.
+    columns: up to 8 entries `video` or `(video, kp_mean)`; video (B, 3, d | 1, H, W) fp32 with contiguous H x W planes and any
+    batch / channel / frame strides (one frame = the reference's `.repeat(1, 1, d, 1, 1)`, read with a frame stride of 0), kp_mean
+    (B, d | 1, K, 2) fp32 with a contiguous (K, 2) tail.  colors: (K, 3) fp32 on the videos' device.
+    Returns uint8 (d, B * H, ncol * W, 3)."""
+    cols = [c if isinstance(c, (tuple, list)) else (c, None) for c in columns]
+    first = cols[0][0]
+    _check_device(first)
+    b, ch, _, h, w = first.shape
+    rec = np.zeros(len(cols), dtype=VIS_COLUMN)
+    keep, k = [], 0
+    for i, (video, kp) in enumerate(cols):
+        if video.dtype != torch.float32 or video.device != first.device:
+            raise ValueError("vis_grid: every video must be a float32 tensor on one device")
+        if video.dim() != 5 or tuple(video.shape[:2]) != (b, ch) or tuple(video.shape[3:]) != (h, w) or video.shape[2] not in (1, d):
+            raise ValueError("vis_grid: column %d has shape %s, expected (%d, %d, %d | 1, %d, %d)"
+                             % (i, tuple(video.shape), b, ch, d, h, w))
+        if video.stride(4) != 1 or video.stride(3) != w or min(video.stride()) < 0:
+            video = video.contiguous()
+        keep.append(video)
+        rec[i]["video"] = video.data_ptr()
+        rec[i]["batch_stride"], rec[i]["chan_stride"] = video.stride(0), video.stride(1)
+        rec[i]["frame_stride"] = video.stride(2) if video.shape[2] > 1 else 0
+        if kp is not None:
+            if kp.dtype != torch.float32 or kp.device != first.device or kp.dim() != 4 or kp.shape[0] != b or kp.shape[3] != 2 \
+                    or kp.shape[1] not in (1, d) or (k and kp.shape[2] != k):
+                raise ValueError("vis_grid: key points of column %d have shape %s, expected (%d, %d | 1, K, 2) float32"
+                                 % (i, tuple(kp.shape), b, d))
+            k = kp.shape[2]
+            if kp.stride(3) != 1 or kp.stride(2) != 2 or min(kp.stride()) < 0:
+                kp = kp.contiguous()
+            keep.append(kp)
+            rec[i]["kp"] = kp.data_ptr()
+            rec[i]["kp_batch_stride"] = kp.stride(0)
+            rec[i]["kp_frame_stride"] = kp.stride(1) if kp.shape[1] > 1 else 0
+    if k and (colors is None or tuple(colors.shape) != (k, 3) or colors.dtype != torch.float32 or colors.device != first.device
+              or not colors.is_contiguous()):
+        raise ValueError("vis_grid: colors must be a contiguous (%d, 3) float32 tensor on the videos' device" % k)
+    if out is None:
+        out = torch.empty(d, b * h, len(cols) * w, 3, dtype=torch.uint8, device=first.device)
+    # the column table is read during the call (it travels in the kernel arguments): `rec` and `keep` only have to live until then
+    _call("mnk_vis_grid", first, int(rec.ctypes.data), len(cols), b, ch, d, h, w, k, float(kp_size), int(bool(draw_border)),
+          _p(colors) if k else None, _p(out))
+    return out
+
+
+def frames_to_strip(video, out=None):
+    """(C = 3, D, H, W) fp32 -> uint8 (H, D * W, 3): the frame strip the evaluation loops save as .png
+    (reconstruction.py:66-68, prediction.py:137-139)."""
+    _check_device(video)
+    if video.dim() != 4 or video.dtype != torch.float32:
+        raise ValueError("frames_to_strip: expected a (3, D, H, W) float32 tensor, got %s %s" % (tuple(video.shape), video.dtype))
+    c, d, h, w = video.shape
+    if video.stride(3) != 1 or video.stride(2) != w or min(video.stride()) < 0:
+        video = video.contiguous()
+    if out is None:
+        out = torch.empty(h, d * w, 3, dtype=torch.uint8, device=video.device)
+    _call("mnk_frames_to_strip", video, _p(video), c, video.stride(0), video.stride(1), d, h, w, _p(out))
+    return out
+
+
 class ClipVarianceFn(_Fn):
     """var * max(clip, sigma_min(var)) / sigma_min(var) on (..., 2, 2) covariances (keypoint_detector.py:62-65,
     modules/util.py:244-255) in one kernel instead of ~25 element-wise launches (+ ~60 in the backward)."""

@@ -34,6 +34,13 @@ def main():
             dist.init_process_group("nccl")            # RCCL over xGMI
         else:
             dist.init_process_group("gloo")
+    # MNK_NATIVE_VISUALIZER=1 (mnk/knobs.py): the script directory's own `logger` module is imported first and its Visualizer
+    # rebound to the device-side one, so `from logger import Logger, Visualizer` and Logger's own use both see it.  Read here
+    # directly: with the switch off nothing is imported that was not imported before.
+    if os.environ.get("MNK_NATIVE_VISUALIZER", "0") == "1":
+        import logger
+        from mnk.visualizer import Visualizer
+        logger.Visualizer = Visualizer
     runpy.run_path(script, run_name="__main__")
 
 
