@@ -394,7 +394,7 @@ int mnk_table_upload(const void* host, void* device, size_t bytes, void* stream)
  * 4 and 5 (call it once before the launches of an iteration); grad_scale multiplies g first (1 / world size after a sum
  * all-reduce).  A descriptor is a plain range of n floats, or -- wp_fwd != NULL -- a
  * (Cout, C0 + C1, 1, 3, 3) convolution weight whose packed forward / data-gradient layouts (mnk_conv3x3_pack_multi's)
- * are written from the updated values in the same pass.  Table in device memory sorted by block_begin; a descriptor owns
+ * are written from the updated values in the same pass, or (ntaps) a (Cout, C0, 1, K, K) one with mnk_conv2d_pack_all's.  Table in device memory sorted by block_begin; a descriptor owns
  * mnk_adam_blocks(...) blocks. */
 typedef struct MnkAdamDesc {
     float* p;
@@ -408,7 +408,8 @@ typedef struct MnkAdamDesc {
     int Cout, C0, C1, block_begin;
     int flags;      /* bit 0: an up-sampled convolution -- emit the packs of its sub-pixel forms (mnk_conv3x3_up_*);
                        bit 1 / bit 2: gt0 / gt1 hold 16 pseudo taps of the sub-pixel weight-gradient form (folded here) */
-    int reserved;
+    int ntaps;      /* 0 or 9: a 3x3 weight; else (<= 16) a K x K weight, ntaps = K * K: mnk_conv2d_pack_all's layouts are
+                       emitted (flags and gt0 / gt1 must be 0) */
     /* optional: the gradient of source 0 / source 1 of a convolution weight taken straight from the tap-major partials of the
      * grouped weight-gradient GEMMs, part[split][tap][Cout][C_source] (mnk_wgrad_grouped_*), summed over gt_splits* <= 3 splits in
      * order -- the bits mnk_wgrad_reduce_multi would have left in `g`, without its pass over them.  NULL: `g` is read. */

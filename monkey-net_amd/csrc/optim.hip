@@ -3,8 +3,8 @@
 // 166+ tensors: 8 multi-tensor launches per iteration + a separate re-pack launch reading every weight again).
 //
 // HBM-bound: per element it reads p, g, m, v and writes p, m, v (28 B); convolution weights additionally leave as their
-// forward / data-gradient GEMM layouts (mnk_conv3x3_pack_multi's tile, straight from the LDS tile the update was made
-// in), which saves re-reading the parameter in a separate pack launch.
+// forward / data-gradient GEMM layouts (mnk_conv3x3_pack_multi's tile, or mnk_conv2d_pack_all's for a K x K weight, straight
+// from the LDS tile the update was made in), which saves re-reading the parameter in a separate pack launch.
 //
 // Update formula = torch/optim/adam.py::_single_tensor_adam (no amsgrad, no weight decay), evaluated in fp32:
 //   m += (g - m) * (1 - b1);  v = b2 * v + (1 - b2) * g * g;
@@ -42,6 +42,37 @@ __global__ void adam_tick_kernel(float* hyper) {
         hyper[4] = (float)((double)hyper[0] / (1.0 - pow(b1, (double)t)));
         hyper[5] = (float)sqrt(1.0 - pow(b2, (double)t));
     }
+}
+
+// ---- K x K convolution weight (the discriminator's 4x4): one 16 (co) x 16 (ci) x ntaps tile, updated and left as
+// mnk_conv2d_pack_all's layouts (plain copies of the updated values, zeros outside the parameter).  NT = ntaps when known at
+// compile time (16: the passes of the block unroll, so the loads of a thread's NT elements are all in flight), else 0
+template <int NT>
+__device__ __forceinline__ void adam_kxk_tile(float* T, const MnkAdamDesc& d, const Hyper& h, int C0p, int C1p, int cc, int cot) {
+    const PackTileGeom g = pack_tile_geom<NT>(d.Cout, d.C0, d.C1, C0p, C1p, d.ntaps, cc, cot);
+    const int ntaps = NT ? NT : g.ntaps, run = 16 * ntaps;
+    const int t = threadIdx.x;
+    constexpr int UN = NT ? NT : 1;
+#pragma unroll UN
+    for (int k = 0; k < ntaps; ++k) {               // 16 * run / 256 = ntaps passes of the block
+        const int i = t + k * 256;
+        const int r = i / run, o = i - r * run;     // row (co), offset inside the row = ci * ntaps + tap
+        const int ci = o / ntaps, tap = o - ci * ntaps;
+        const int co = g.co0 + r;
+        float p = 0.f;
+        if (co < d.Cout && g.ci0 + ci < g.Cs) {
+            const size_t idx = ((size_t)co * g.Cin + g.cstart + g.ci0) * ntaps + o;
+            p = d.p[idx];
+            float m = d.m[idx], v = d.v[idx];
+            adam_update(p, d.g[idx], m, v, h);
+            d.p[idx] = p;
+            d.m[idx] = m;
+            d.v[idx] = v;
+        }
+        T[r * g.cos + ci * g.ntp + tap] = p;
+    }
+    __syncthreads();
+    pack_tile_emit<NT>(T, g, d.wp_fwd, d.wp_d0, d.wp_d1, d.Cout, cc, cot);
 }
 
 constexpr int PLAIN_PER_BLOCK = 4096;       // floats of a plain range handled by one block (256 threads x 4 float4)
@@ -94,9 +125,16 @@ __global__ void __launch_bounds__(256) adam_multi_kernel(const MnkAdamDesc* __re
         }
         return;
     }
-    // ---- 3x3 convolution weight: one 16 (co) x 16 (ci) x 9 tile, updated and re-packed ---------------------------
     const int C0p = (d.C0 + 15) & ~15, C1p = d.C1 > 0 ? (d.C1 + 15) & ~15 : 0, tiles_x = (C0p + C1p) / 16;
     const int cot = local / tiles_x, cc = local - cot * tiles_x;
+    if (d.ntaps && d.ntaps != 9) {
+        if (d.ntaps == 16)
+            adam_kxk_tile<16>(T, d, h, C0p, C1p, cc, cot);
+        else
+            adam_kxk_tile<0>(T, d, h, C0p, C1p, cc, cot);
+        return;
+    }
+    // ---- 3x3 convolution weight: one 16 (co) x 16 (ci) x 9 tile, updated and re-packed ---------------------------
     const PackTileGeom g = pack_tile_geom<9>(d.Cout, d.C0, d.C1, C0p, C1p, 9, cc, cot);
     constexpr int run = 16 * 9, NI = 16 * run / 256;        // nine elements per thread
     static_assert(16 * run % 256 == 0, "a tile is a whole number of passes of the block");

@@ -255,7 +255,7 @@ class Concat2Fn(_Fn):
 _PACK_CACHE = {}
 _PACK_EPOCH = [0]
 _PACK_REG = {}                     # id(parameter) -> _PackEntry
-_PACK_TABLE = {"dirty": True, "descs": None, "n": 0, "tiles": 0, "entries": (), "keep": []}
+_PACK_TABLE = {"dirty": True, "descs": None, "n": 0, "tiles": 0, "entries": (), "kxk": (), "keep": []}
 _PACK_REG_VERSION = [0]            # bumped whenever an entry (or one of its buffers) is created or dropped
 
 
@@ -418,35 +418,45 @@ def _packed_fwd_weight(weight, cout, c0, c1, up=False):
 
 class _PackEntry:
     """Persistent packed copies (forward + data-gradient layouts) of one conv parameter used by training forwards."""
-    __slots__ = ("wref", "wptr", "meta", "wp", "wd", "stamp", "__weakref__")
+    __slots__ = ("wref", "wptr", "meta", "ntaps", "wp", "wd", "stamp", "__weakref__")
 
-    def fresh(self, weight, meta, need):
-        return (self.wref() is weight and self.wptr == weight.data_ptr() and self.meta == meta
-                and self.stamp is not None and self.stamp == weight._version
+    def same(self, weight, meta, ntaps):
+        return self.wref() is weight and self.wptr == weight.data_ptr() and self.meta == meta and self.ntaps == ntaps
+
+    def fresh(self, weight, meta, need, ntaps=9):
+        return (self.same(weight, meta, ntaps) and self.stamp is not None and self.stamp == weight._version
                 and all(self.wd[i] is not None for i in (0, 1) if need[i]))
 
+    def pack(self):
+        """one launch for this layer alone (mnk_conv2d_pack_all: a K x K weight, ntaps = K * K <= 16)"""
+        w, (cout, c0, c1, _) = self.wref(), self.meta
+        _call("mnk_conv2d_pack_all", w, _p(w), _p(self.wp), _p(self.wd[0]), _p(self.wd[1]), cout, c0, c1, self.ntaps)
 
 
-def _pack_entry(weight, cout, c0, c1, need, up=False):
+
+def _pack_entry(weight, cout, c0, c1, need, up=False, ntaps=9):
     """The (packed, up to date) registry entry of `weight`: packs with one per-layer launch unless the entry is fresh
     (repack_registered() ran since the last optimiser step).  up: the packs of the sub-pixel forms of an up-sampled
-    convolution (mnk_conv3x3_up_fwd / _up_dgrad) instead of the 3x3 layouts."""
+    convolution (mnk_conv3x3_up_fwd / _up_dgrad) instead of the 3x3 layouts.  ntaps != 9: a K x K weight (ConvKxKFn)."""
     meta = (cout, c0, c1, bool(up))
+    kxk = ntaps != 9
     form, dform = (_FORMS["up"], _FORMS["up_dgrad"]) if up else (_FORMS["3x3"], _FORMS["3x3"])
     e = _PACK_REG.get(id(weight))
-    if e is not None and e.fresh(weight, meta, need):
+    if e is not None and e.fresh(weight, meta, need, ntaps):
         return e
-    if (e is not None and e.wref() is weight and e.wptr == weight.data_ptr() and e.meta == meta
+    if (e is not None and e.same(weight, meta, ntaps)
             and all(e.wd[i] is not None for i in (0, 1) if need[i])):
         # a known layer gone stale (an optimiser stepped): the first such layer of an iteration re-packs EVERY registered
         # parameter in one launch -- a user-owned loop (the reference's train.py) then pays one pack launch per iteration
         # instead of one (to three) per convolution, as mnk.engine.TrainStep does at the start of its iterations
-        if repack_registered() and e.fresh(weight, meta, need):
+        if repack_registered() and e.fresh(weight, meta, need, ntaps):
             return e
-    if e is None or e.wref() is not weight or e.wptr != weight.data_ptr() or e.meta != meta:
+    if e is None or not e.same(weight, meta, ntaps):
         e = _PackEntry()
         e.wref, e.wptr, e.meta, e.wd, e.stamp = weakref.ref(weight), weight.data_ptr(), meta, [None, None], None
-        e.wp = torch.empty(_query(form.packed, cout, c0, c1), dtype=torch.float32, device=weight.device)
+        e.ntaps = ntaps
+        nf = _query(_FORMS["kxk"].packed, cout, c0, c1, ntaps) if kxk else _query(form.packed, cout, c0, c1)
+        e.wp = torch.empty(nf, dtype=torch.float32, device=weight.device)
         key = id(weight)
         _PACK_REG[key] = e
         weakref.finalize(weight, _drop_pack_entry, key, weakref.ref(e))
@@ -454,11 +464,16 @@ def _pack_entry(weight, cout, c0, c1, need, up=False):
         _PACK_REG_VERSION[0] += 1
     for i, cc in enumerate((c0, c1)):
         if need[i] and e.wd[i] is None:
-            nd = _query(dform.packed, cout, cc) if up else _query(dform.packed, cc, cout, 0)
+            if kxk:
+                nd = _query(_FORMS["kxk"].packed, cc, cout, 0, ntaps)
+            else:
+                nd = _query(dform.packed, cout, cc) if up else _query(dform.packed, cc, cout, 0)
             e.wd[i] = torch.empty(nd, dtype=torch.float32, device=weight.device)
             _PACK_TABLE["dirty"] = True
             _PACK_REG_VERSION[0] += 1
-    if up:
+    if kxk:
+        e.pack()
+    elif up:
         _call(form.pack, weight, _p(weight), _p(e.wp), cout, c0, c1)
         for i, (cs, cc) in enumerate(((0, c0), (c0, c1))):
             if e.wd[i] is not None:
@@ -477,7 +492,8 @@ def _drop_pack_entry(key, eref):
 
 
 def repack_registered(only_if_stale=False):
-    """Re-pack EVERY registered conv parameter in one launch (mnk_conv3x3_pack_multi) -- the start of a training
+    """Re-pack EVERY registered conv parameter: the 3x3 ones in one launch (mnk_conv3x3_pack_multi), each K x K one (the
+    discriminator's four) with a launch of its own -- the start of a training
     iteration (mnk.engine.TrainStep): ~40 per-layer pack launches become one.  Parameters first seen later in the
     iteration (and everything, when called under stream capture before the table exists) fall back to per-layer packs.
     only_if_stale: nothing to do when every entry is still fresh (the optimiser kernel of mnk.optim wrote the packs)."""
@@ -499,6 +515,8 @@ def repack_registered(only_if_stale=False):
         if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
             return False                     # building the table needs a host-to-device copy
         entries = [e for e in entries if e.wp.device == dev]
+        kxk = tuple(e for e in entries if e.ntaps != 9)
+        entries = [e for e in entries if e.ntaps == 9]
         rec = np.zeros(len(entries), dtype=np.dtype([("p", "<u8", 4), ("i", "<i4", 6)]))
         tiles = 0
         for k, e in enumerate(entries):
@@ -509,11 +527,15 @@ def repack_registered(only_if_stale=False):
             tiles += ((ceil16(c0) + (ceil16(c1) if c1 else 0)) // 16) * ((cout + 15) // 16)
         descs = torch.from_numpy(rec.view(np.uint8).reshape(-1).copy()).to(dev)
         t["keep"].append(descs)              # captured graphs hold raw pointers to earlier tables: never free them
-        t.update(dirty=False, descs=descs, n=len(entries), tiles=tiles, entries=tuple(entries))
-    if not t["n"]:
+        t.update(dirty=False, descs=descs, n=len(entries), tiles=tiles, entries=tuple(entries), kxk=kxk)
+    if not t["n"] and not t["kxk"]:
         return False
-    _call("mnk_conv3x3_pack_multi", t["descs"], _p(t["descs"]), t["n"], t["tiles"])
-    for e in t["entries"]:
+    if t["n"]:
+        _call("mnk_conv3x3_pack_multi", t["descs"], _p(t["descs"]), t["n"], t["tiles"])
+    for e in t["kxk"]:
+        if e.wref() is not None:
+            e.pack()
+    for e in t["entries"] + t["kxk"]:
         w = e.wref()
         if w is not None:
             e.stamp = w._version
@@ -1197,14 +1219,20 @@ class ConvKxKFn(_Fn):
         ho, wo = hi + 2 * pad - kh + 1, wi + 2 * pad - kw + 1
         nt = kh * kw
         form = _FORMS["kxk"]
-        wp = SCRATCH.get("pack", _query(form.packed, cout, cin, 0, nt), x)
         ctx.wd = None
-        if ctx.needs_input_grad[0] and nt <= 16:
-            # forward and data-gradient layouts in ONE launch; the latter serves every backward pass through this node (the
-            # generator pass and the discriminator pass of one iteration read the same, not yet updated, weights)
+        if nt <= 16 and nt != 9 and weight.requires_grad and weight.is_contiguous():
+            # a training forward: the registry entry of the weight (forward and data-gradient layouts: written by the
+            # optimiser kernel after its update, else packed here in ONE launch); the data-gradient layout serves every backward
+            # pass through this node (the generator pass and the discriminator pass of one iteration read the same, not yet
+            # updated, weights)
+            e = _pack_entry(weight, cout, cin, 0, [bool(ctx.needs_input_grad[0]), False], ntaps=nt)
+            wp, ctx.wd = e.wp, e.wd[0]
+        elif ctx.needs_input_grad[0] and nt <= 16:
+            wp = SCRATCH.get("pack", _query(form.packed, cout, cin, 0, nt), x)
             ctx.wd = torch.empty(_query(form.packed, cin, cout, 0, nt), dtype=torch.float32, device=x.device)
             _call("mnk_conv2d_pack_all", x, _p(weight), _p(wp), _p(ctx.wd), None, cout, cin, 0, nt)
         else:
+            wp = SCRATCH.get("pack", _query(form.packed, cout, cin, 0, nt), x)
             _call(form.pack, x, _p(weight), _p(wp), cout, cin, 0, nt)
         # flags = MNK_CONV_CLEAN_PADS: x is an act of this module (zero pad channels) -> the K x K buffer-load loader
         y, _ = _gemm_launch("kxk", x, cin, None, 0, wp, bias, None, n, ho, wo, cout, 2, kxk=(hi, wi, kh, kw, pad))

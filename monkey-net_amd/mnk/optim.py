@@ -2,8 +2,8 @@
 torch.optim.Adam(params, lr, betas=(0.5, 0.999)) + the implicit gradient reductions are in train.py:81-83,118-136.
 
 `MnkAdam` is a torch.optim.Optimizer (param_groups, state_dict, lr schedulers keep working) whose step is ONE kernel
-launch over a descriptor table (mnk_adam_multi) that also writes the packed GEMM layouts of every 3x3 convolution weight
-for the next iteration.  It owns three flat fp32 buffers -- gradients, exp_avg, exp_avg_sq -- with one 16-byte aligned
+launch over a descriptor table (mnk_adam_multi) that also writes the packed GEMM layouts of every 3x3 and K x K convolution
+weight for the next iteration.  It owns three flat fp32 buffers -- gradients, exp_avg, exp_avg_sq -- with one 16-byte aligned
 slice per parameter:
 
 * gradients land in their slice ("sink") without copies: the weight-gradient GEMMs of the convolutions run with
@@ -27,7 +27,7 @@ from . import ops as mops
 
 ADAM_DESC = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("n", "<i8"), ("wp_fwd", "<u8"),
                       ("wp_d0", "<u8"), ("wp_d1", "<u8"), ("Cout", "<i4"), ("C0", "<i4"), ("C1", "<i4"),
-                      ("block_begin", "<i4"), ("flags", "<i4"), ("reserved", "<i4"), ("gt0", "<u8"), ("gt1", "<u8"),
+                      ("block_begin", "<i4"), ("flags", "<i4"), ("ntaps", "<i4"), ("gt0", "<u8"), ("gt1", "<u8"),
                       ("gt_splits0", "<i4"), ("gt_splits1", "<i4")])
 REDUCE_DESC = np.dtype([("part", "<u8"), ("dw", "<u8"), ("layout", "<i4"), ("splits", "<i4"), ("ntaps", "<i4"),
                         ("Cout", "<i4"), ("C", "<i4"), ("Cin_total", "<i4"), ("c_start", "<i4"), ("accumulate", "<i4"),
@@ -48,6 +48,11 @@ def _device_table(rec, device, keep):
     t = torch.from_numpy(rec.view(np.uint8).reshape(-1).copy()).to(device)
     keep.append(t)          # captured graphs hold raw pointers to earlier tables: never free them
     return t
+
+
+def _desc_taps(e):
+    """MnkAdamDesc::ntaps of a packed-weight entry: 0 = a 3x3 weight, K * K = a K x K one (the discriminator's 4x4)"""
+    return 0 if e.ntaps == 9 else e.ntaps
 
 
 _BG_STREAMS = {}
@@ -428,7 +433,7 @@ class MnkAdam(torch.optim.Optimizer, FlatGrads):
                         flags |= (2 << si) if r["row"][2] == 2 else 0
                 rows.append((p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), e.wp.data_ptr(),
                              e.wd[0].data_ptr() if e.wd[0] is not None else 0,
-                             e.wd[1].data_ptr() if e.wd[1] is not None else 0, cout, c0, c1, blocks, flags, 0,
+                             e.wd[1].data_ptr() if e.wd[1] is not None else 0, cout, c0, c1, blocks, flags, _desc_taps(e),
                              gt[0][0], gt[1][0], gt[0][1], gt[1][1]))
                 entries.append(e)
             else:
@@ -640,7 +645,8 @@ class AdoptedAdam:
                     nb = _lib.lib().query("mnk_adam_blocks", 0, cout, c0, c1, 1)
                     rows.append((p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(),
                                  e.wp.data_ptr(), e.wd[0].data_ptr() if e.wd[0] is not None else 0,
-                                 e.wd[1].data_ptr() if e.wd[1] is not None else 0, cout, c0, c1, blocks, int(up), 0, 0, 0, 0, 0))
+                                 e.wd[1].data_ptr() if e.wd[1] is not None else 0, cout, c0, c1, blocks, int(up), _desc_taps(e),
+                                 0, 0, 0, 0))
                     entries.append(e)
                 else:
                     nb = _lib.lib().query("mnk_adam_blocks", p.numel(), 0, 0, 0, 0)
