@@ -159,35 +159,55 @@ __device__ __forceinline__ void lane_colsum_pair(const float* __restrict__ p, in
     a2 = (t0 + t1) + (t2 + t3);
 }
 
+// The second stage's wavefront tree: the 64 lane sums of each of N columns (acc: by lane_colsum / lane_colsum_pair) -> their total,
+// in fp64 through LDS: 8 groups of 8 consecutive lanes, then the 8 group totals in order.  Every thread of the block calls it; the
+// lanes with `want` leave with the totals in acc (lane 0 of a wavefront that has a column, or -- the exchange needs the total
+// wave-wide -- every lane: the bits are the same).
+template <int N>
+__device__ __forceinline__ void wave_tree_sum(double (&sm)[N][256], double (&acc)[N], bool want) {
+    const int lane = threadIdx.x & 63, base = threadIdx.x & ~63;
+#pragma unroll
+    for (int k = 0; k < N; ++k) sm[k][threadIdx.x] = acc[k];
+    __syncthreads();
+    if (lane < 8) {
+        double t[N];
+#pragma unroll
+        for (int k = 0; k < N; ++k) t[k] = 0.0;
+        for (int j = 0; j < 8; ++j)
+#pragma unroll
+            for (int k = 0; k < N; ++k) t[k] += sm[k][base + lane * 8 + j];
+#pragma unroll
+        for (int k = 0; k < N; ++k) sm[k][base + lane * 8] = t[k];
+    }
+    __syncthreads();
+    if (want) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) acc[k] = 0.0;
+        for (int j = 0; j < 8; ++j)
+#pragma unroll
+            for (int k = 0; k < N; ++k) acc[k] += sm[k][base + j * 8];
+    }
+}
+
 // one wavefront per output column: lanes stride over the row-block partials (fp64 accumulation), the 64 lane sums are
 // combined through LDS.  (A serial loop per column was 44 % of the step time in the first MI355X profile.)
 __global__ void __launch_bounds__(256) colsum2_final_kernel(const float* __restrict__ partial, int row_blocks, int ld,
                                                             int C, int frames, float* __restrict__ sums, int nwhich) {
     // sums[which][frame][c] = sum_rb partial[frame][rb][which][c], which < nwhich (1: first sum only)
-    __shared__ double sm[256];
+    __shared__ double sm[1][256];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = blockIdx.x * 4 + wave;
     const int FC = frames * C;
-    double acc = 0.0;
+    double acc[1] = {0.0};
     if (i < nwhich * FC) {
         const int which = i / FC, rem = i - which * FC;
         const int f = rem / C, c = rem - f * C;
         const float* pb = partial + (long)f * row_blocks * 2 * ld;
-        acc = lane_colsum(pb + (long)which * ld + c, lane, row_blocks, 2L * ld);
+        acc[0] = lane_colsum(pb + (long)which * ld + c, lane, row_blocks, 2L * ld);
     }
-    sm[threadIdx.x] = acc;
-    __syncthreads();
-    if (lane < 8) {
-        double t = 0.0;
-        for (int j = 0; j < 8; ++j) t += sm[wave * 64 + lane * 8 + j];
-        sm[wave * 64 + lane * 8] = t;
-    }
-    __syncthreads();
-    if (lane == 0 && i < nwhich * FC) {
-        double t = 0.0;
-        for (int j = 0; j < 8; ++j) t += sm[wave * 64 + j * 8];
-        sums[i] = (float)t;
-    }
+    const bool writer = lane == 0 && i < nwhich * FC;
+    wave_tree_sum(sm, acc, writer);
+    if (writer) sums[i] = (float)acc[0];
 }
 
 // colsum2_final_kernel with the SyncBN exchange of one node inside (csrc/p2p.hip's protocol): the wavefront that finishes the
@@ -199,28 +219,19 @@ __global__ void __launch_bounds__(256) colsum2_final_sync_kernel(const float* __
                                                                  float* __restrict__ local, float* __restrict__ global_sums,
                                                                  PeerTable peers, int rank, int world, unsigned* state,
                                                                  unsigned long long timeout_ticks) {
-    __shared__ double sm[256];
+    __shared__ double sm[1][256];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = blockIdx.x * 4 + wave;
     const unsigned seq = state[0] + 1;
     const int slot = (int)(seq % P2P_SLOTS);
-    double acc = 0.0;
+    double acc[1] = {0.0};
     if (i < 2 * C) {
         const int which = i / C, c = i - which * C;
-        acc = lane_colsum(partial + (long)which * ld + c, lane, row_blocks, 2L * ld);
+        acc[0] = lane_colsum(partial + (long)which * ld + c, lane, row_blocks, 2L * ld);
     }
-    sm[threadIdx.x] = acc;
-    __syncthreads();
-    if (lane < 8) {
-        double t = 0.0;
-        for (int j = 0; j < 8; ++j) t += sm[wave * 64 + lane * 8 + j];
-        sm[wave * 64 + lane * 8] = t;
-    }
-    __syncthreads();
+    wave_tree_sum(sm, acc, i < 2 * C);      // every lane: the bits colsum2_final_kernel's lane 0 makes
     if (i < 2 * C) {                       // (wave-uniform)
-        double t = 0.0;
-        for (int j = 0; j < 8; ++j) t += sm[wave * 64 + j * 8];       // every lane: the bits colsum2_final_kernel's lane 0 makes
-        const float mine = (float)t;
+        const float mine = (float)acc[0];
         const float all = p2p_exchange_value(peers, rank, world, slot, seq, i, mine, state, timeout_ticks);
         if (lane == 0) {
             if (local) local[i] = mine;
@@ -230,18 +241,33 @@ __global__ void __launch_bounds__(256) colsum2_final_sync_kernel(const float* __
     p2p_finish_launch(state, seq);
 }
 
-static int launch_final_sync(void* p2p, const float* partial, int row_blocks, int ld, int C, float* local, float* global_sums,
-                             int timeout_ms, hipStream_t s) {
+// what a launch that carries the exchange needs from a connected handle (p2p.hip)
+struct P2PLaunch {
     PeerTable peers;
-    int rank = 0, world = 0;
-    unsigned* state = nullptr;
-    if (!p2p_launch_info(p2p, &peers, &rank, &world, &state) || 2 * C > P2P_MAXF || timeout_ms <= 0) {
-        set_error("synchronised BatchNorm statistics: the peer-to-peer exchange is not connected, or more than %d channels",
-                  P2P_MAXF / 2);
+    int rank, world;
+    unsigned* state;
+    unsigned long long timeout_ticks;
+};
+
+// fills `pl` for entry point `who`, whose exchange moves the 2 * C sums of C channels; MNK_ECOMM when it cannot
+static int p2p_launch(const char* who, void* p2p, int C, int timeout_ms, P2PLaunch* pl) {
+    pl->rank = pl->world = 0;
+    pl->state = nullptr;
+    if (!p2p_launch_info(p2p, &pl->peers, &pl->rank, &pl->world, &pl->state) || 2 * C > P2P_MAXF || timeout_ms <= 0) {
+        set_error("%s: the peer-to-peer exchange is not connected, or more than %d channels", who, P2P_MAXF / 2);
         return MNK_ECOMM;
     }
+    pl->timeout_ticks = (unsigned long long)timeout_ms * 100000ull;      // the 100 MHz wall clock
+    return MNK_OK;
+}
+
+static int launch_final_sync(const char* who, void* p2p, const float* partial, int row_blocks, int ld, int C, float* local,
+                             float* global_sums, int timeout_ms, hipStream_t s) {
+    P2PLaunch pl;
+    const int rc = p2p_launch(who, p2p, C, timeout_ms, &pl);
+    if (rc != MNK_OK) return rc;
     hipLaunchKernelGGL(colsum2_final_sync_kernel, dim3(ceil_div(2 * C, 4)), dim3(256), 0, s, partial, row_blocks, ld, C, local,
-                       global_sums, peers, rank, world, state, (unsigned long long)timeout_ms * 100000ull);
+                       global_sums, pl.peers, pl.rank, pl.world, pl.state, pl.timeout_ticks);
     return MNK_OK;
 }
 
@@ -318,6 +344,27 @@ struct BwdLoader {
     }
 };
 
+// The statistics of one channel from its two sums over `count` values -- THE finalisation arithmetic of every training-mode
+// form: fp64 mean and variance (clamped at zero), fp32 inverse standard deviation.
+struct BnStats {
+    float mean, invstd;
+    double var;           // biased, fp64: what the running-variance update starts from
+};
+__device__ __forceinline__ BnStats bn_finalize(float s1, float s2, double count, float eps) {
+    const double m = (double)s1 / count;
+    double v = (double)s2 / count - m * m;
+    if (v < 0.0) v = 0.0;
+    const float mf = (float)m, vf = (float)v;
+    return BnStats{mf, 1.0f / sqrtf(vf + eps), v};
+}
+// ... and the running statistics of channel c after this batch (the variance unbiased: count > 1)
+__device__ __forceinline__ void bn_update_running(float* running_mean, float* running_var, int c, float momentum, const BnStats& st,
+                                                  double count) {
+    const float unbiased = (float)(st.var * count / (count - 1.0));
+    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * st.mean;
+    running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
+}
+
 // C = number of statistics entries (channels, or frames*channels for per-frame statistics); gamma has gamma_mod entries
 __global__ void __launch_bounds__(256) bn_finalize_kernel(const float* __restrict__ sums, double count,
                                                           const float* __restrict__ gamma, int gamma_mod,
@@ -326,19 +373,11 @@ __global__ void __launch_bounds__(256) bn_finalize_kernel(const float* __restric
                                                           float* invstd, float* scale) {
     int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    double m = (double)sums[c] / count;
-    double v = (double)sums[C + c] / count - m * m;
-    if (v < 0.0) v = 0.0;
-    float mf = (float)m, vf = (float)v;
-    float is = 1.0f / sqrtf(vf + eps);
-    mean[c] = mf;
-    invstd[c] = is;
-    scale[c] = gamma[c % gamma_mod] * is;
-    if (update_running) {
-        float unbiased = (float)(v * count / (count - 1.0));
-        running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mf;
-        running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
-    }
+    const BnStats st = bn_finalize(sums[c], sums[C + c], count, eps);
+    mean[c] = st.mean;
+    invstd[c] = st.invstd;
+    scale[c] = gamma[c % gamma_mod] * st.invstd;
+    if (update_running) bn_update_running(running_mean, running_var, c, momentum, st, count);
 }
 
 // colsum2_final + bn_finalize in one launch (single-process BatchNorm: nothing sits between the two): one wavefront
@@ -352,48 +391,24 @@ __global__ void __launch_bounds__(256) bn_final_finalize_kernel(const float* __r
     __shared__ double sm[2][256];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = blockIdx.x * 4 + wave;
-    double a1 = 0.0, a2 = 0.0;
+    double acc[2] = {0.0, 0.0};
     if (c < C) {
-        lane_colsum_pair(partial + c, ld, lane, row_blocks, 2L * ld, a1, a2);      // the bits of lane_colsum per sum
+        lane_colsum_pair(partial + c, ld, lane, row_blocks, 2L * ld, acc[0], acc[1]);      // the bits of lane_colsum per sum
     }
-    sm[0][threadIdx.x] = a1;
-    sm[1][threadIdx.x] = a2;
-    __syncthreads();
-    if (lane < 8) {
-        double t1 = 0.0, t2 = 0.0;
-        for (int j = 0; j < 8; ++j) {
-            t1 += sm[0][wave * 64 + lane * 8 + j];
-            t2 += sm[1][wave * 64 + lane * 8 + j];
-        }
-        sm[0][wave * 64 + lane * 8] = t1;
-        sm[1][wave * 64 + lane * 8] = t2;
-    }
-    __syncthreads();
-    if (lane == 0 && c < C) {
-        double t1 = 0.0, t2 = 0.0;
-        for (int j = 0; j < 8; ++j) {
-            t1 += sm[0][wave * 64 + j * 8];
-            t2 += sm[1][wave * 64 + j * 8];
-        }
+    const bool writer = lane == 0 && c < C;
+    wave_tree_sum(sm, acc, writer);
+    if (writer) {
         // the same arithmetic as colsum2_final_kernel -> bn_finalize_kernel (sums round-trip through fp32)
-        const float s1 = (float)t1, s2 = (float)t2;
+        const float s1 = (float)acc[0], s2 = (float)acc[1];
         if (sums) {
             sums[c] = s1;
             sums[C + c] = s2;
         }
-        const double m = (double)s1 / count;
-        double v = (double)s2 / count - m * m;
-        if (v < 0.0) v = 0.0;
-        const float mf = (float)m, vf = (float)v;
-        const float is = 1.0f / sqrtf(vf + eps);
-        mean[c] = mf;
-        invstd[c] = is;
-        scale[c] = gamma[c] * is;
-        if (update_running) {
-            const float unbiased = (float)(v * count / (count - 1.0));
-            running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mf;
-            running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
-        }
+        const BnStats st = bn_finalize(s1, s2, count, eps);
+        mean[c] = st.mean;
+        invstd[c] = st.invstd;
+        scale[c] = gamma[c] * st.invstd;
+        if (update_running) bn_update_running(running_mean, running_var, c, momentum, st, count);
     }
 }
 
@@ -411,6 +426,57 @@ __global__ void __launch_bounds__(256) bn_eval_coeffs_kernel(const float* __rest
 
 __device__ __forceinline__ float act_apply(float v, float slope) {   // slope < 0: identity; 0: ReLU; > 0: LeakyReLU
     return (slope >= 0.f && !(v > 0.f)) ? v * slope : v;
+}
+
+// z = act((y - mean) * scale + beta) -- THE apply formula of every forward form; bn_apply4: of one channel quad
+__device__ __forceinline__ float bn_apply1(float v, float m, float sc, float be, float slope) {
+    return act_apply(fmaf(v - m, sc, be), slope);
+}
+__device__ __forceinline__ float4 bn_apply4(float4 v, float4 m, float4 sc, float4 be, float slope) {
+    return make_float4(bn_apply1(v.x, m.x, sc.x, be.x, slope), bn_apply1(v.y, m.y, sc.y, be.y, slope),
+                       bn_apply1(v.z, m.z, sc.z, be.z, slope), bn_apply1(v.w, m.w, sc.w, be.w, slope));
+}
+// ... and the (1,2,2) average pool behind it: px(dy, dx) = the pixels of the 2x2 window, added in row order, times 1/4
+template <class Px>
+__device__ __forceinline__ float4 bn_apply4_pool(Px px, float4 m, float4 sc, float4 be, float slope) {
+    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx) {
+            const float4 v = px(dy, dx);
+            o.x += bn_apply1(v.x, m.x, sc.x, be.x, slope);
+            o.y += bn_apply1(v.y, m.y, sc.y, be.y, slope);
+            o.z += bn_apply1(v.z, m.z, sc.z, be.z, slope);
+            o.w += bn_apply1(v.w, m.w, sc.w, be.w, slope);
+        }
+    o.x *= 0.25f;
+    o.y *= 0.25f;
+    o.z *= 0.25f;
+    o.w *= 0.25f;
+    return o;
+}
+// the 2x2 window of a folded NHWC map of width W whose first pixel's quad is at yb
+__device__ __forceinline__ float4 ld4_window(const float* yb, int W, int ld_y, int dy, int dx) {
+    return *reinterpret_cast<const float4*>(yb + ((long)dy * W + dx) * ld_y);
+}
+
+// dy = scale * (g - sum_g / n - xhat * sum_gx / n) of one channel quad (k1, k2: the two means) -- THE data gradient of every
+// backward form
+__device__ __forceinline__ float4 bn_dx4(float4 g, float4 xh, float4 sc, float4 k1, float4 k2) {
+    return make_float4(sc.x * (g.x - k1.x - xh.x * k2.x), sc.y * (g.y - k1.y - xh.y * k2.y), sc.z * (g.z - k1.z - xh.z * k2.z),
+                       sc.w * (g.w - k1.w - xh.w * k2.w));
+}
+__device__ __forceinline__ float4 f4_scale(float4 a, float k) { return make_float4(a.x * k, a.y * k, a.z * k, a.w * k); }
+
+// a quad of which only the first `rem` lanes are channels: the pad lanes become zero
+__device__ __forceinline__ void zero_pad_lanes(float4& v, int rem) {
+    if (rem < 4) {
+        if (rem < 1) v.x = 0.f;
+        if (rem < 2) v.y = 0.f;
+        if (rem < 3) v.z = 0.f;
+        v.w = 0.f;
+    }
 }
 
 // thread (tx = channel quad, ty = output pixel lane): the per-channel constants stay in registers
@@ -457,22 +523,14 @@ __global__ void __launch_bounds__(256) bn_act_fwd_kernel(const float* __restrict
         for (int e = 0; e < 4; ++e) {
             const int c = q * 4 + e;
             if (c >= C) continue;
-            const double mu = (double)fin.sums[c] / fin.count;
-            double var = (double)fin.sums[C + c] / fin.count - mu * mu;
-            if (var < 0.0) var = 0.0;
-            const float mf = (float)mu, vf = (float)var;
-            const float is = 1.0f / sqrtf(vf + fin.eps);
-            mm[e] = mf;
-            ss[e] = fin.gamma[c] * is;
+            const BnStats st = bn_finalize(fin.sums[c], fin.sums[C + c], fin.count, fin.eps);
+            mm[e] = st.mean;
+            ss[e] = fin.gamma[c] * st.invstd;
             if (blockIdx.y == 0 && ty == 0) {
-                fin.mean[c] = mf;
-                fin.invstd[c] = is;
+                fin.mean[c] = st.mean;
+                fin.invstd[c] = st.invstd;
                 fin.scale[c] = ss[e];
-                if (fin.update_running) {
-                    const float unbiased = (float)(var * fin.count / (fin.count - 1.0));
-                    fin.running_mean[c] = (1.f - fin.momentum) * fin.running_mean[c] + fin.momentum * mf;
-                    fin.running_var[c] = (1.f - fin.momentum) * fin.running_var[c] + fin.momentum * unbiased;
-                }
+                if (fin.update_running) bn_update_running(fin.running_mean, fin.running_var, c, fin.momentum, st, fin.count);
             }
         }
         m = make_float4(mm[0], mm[1], mm[2], mm[3]);
@@ -493,28 +551,10 @@ __global__ void __launch_bounds__(256) bn_act_fwd_kernel(const float* __restrict
             const int wo = (int)(up - t * (unsigned)Wo);
             const unsigned n = t / (unsigned)Ho;
             const int ho = (int)(t - n * (unsigned)Ho);
-            o = make_float4(0.f, 0.f, 0.f, 0.f);
             const float* yb = y + (((long)n * H + 2 * ho) * W + 2 * wo) * ld_y + q * 4;
-#pragma unroll
-            for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-                for (int dx = 0; dx < 2; ++dx) {
-                    const float4 v = *reinterpret_cast<const float4*>(yb + ((long)dy * W + dx) * ld_y);
-                    o.x += act_apply(fmaf(v.x - m.x, sc.x, be.x), slope);
-                    o.y += act_apply(fmaf(v.y - m.y, sc.y, be.y), slope);
-                    o.z += act_apply(fmaf(v.z - m.z, sc.z, be.z), slope);
-                    o.w += act_apply(fmaf(v.w - m.w, sc.w, be.w), slope);
-                }
-            o.x *= 0.25f;
-            o.y *= 0.25f;
-            o.z *= 0.25f;
-            o.w *= 0.25f;
+            o = bn_apply4_pool([=](int dy, int dx) { return ld4_window(yb, W, ld_y, dy, dx); }, m, sc, be, slope);
         } else {
-            const float4 v = *reinterpret_cast<const float4*>(y + p * ld_y + q * 4);
-            o.x = act_apply(fmaf(v.x - m.x, sc.x, be.x), slope);
-            o.y = act_apply(fmaf(v.y - m.y, sc.y, be.y), slope);
-            o.z = act_apply(fmaf(v.z - m.z, sc.z, be.z), slope);
-            o.w = act_apply(fmaf(v.w - m.w, sc.w, be.w), slope);
+            o = bn_apply4(*reinterpret_cast<const float4*>(y + p * ld_y + q * 4), m, sc, be, slope);
         }
         float* zp = z + p * ld_z + z_off + q * 4;
         if (vec_store && (rem >= 4 || owns_pads)) {   // guarded parameter loads make the pad lanes of `o` zero
@@ -561,24 +601,15 @@ __global__ void __launch_bounds__(256) bn_act_bwd_apply_kernel(BwdLoader L, cons
             if (training) {
                 k1 = ld4_guard(sums + po, q, C);
                 k2 = ld4_guard(sums + FC + po, q, C);
-                k1 = make_float4(k1.x * inv, k1.y * inv, k1.z * inv, k1.w * inv);
-                k2 = make_float4(k2.x * inv, k2.y * inv, k2.z * inv, k2.w * inv);
+                k1 = f4_scale(k1, inv);
+                k2 = f4_scale(k2, inv);
             }
         }
         float4 g, xh;
         L.load(r, q, st, g, xh);
-        float4 o;
-        o.x = sc.x * (g.x - k1.x - xh.x * k2.x);
-        o.y = sc.y * (g.y - k1.y - xh.y * k2.y);
-        o.z = sc.z * (g.z - k1.z - xh.z * k2.z);
-        o.w = sc.w * (g.w - k1.w - xh.w * k2.w);
+        float4 o = bn_dx4(g, xh, sc, k1, k2);
         if (addend) o = f4_add(o, *reinterpret_cast<const float4*>(addend + r * ld_add + q * 4));
-        const int rem = C - q * 4;
-        if (rem < 4) {  // keep pad channels of dy at zero
-            if (rem < 2) o.y = 0.f;
-            if (rem < 3) o.z = 0.f;
-            o.w = 0.f;
-        }
+        zero_pad_lanes(o, C - q * 4);       // keep pad channels of dy at zero
         *reinterpret_cast<float4*>(dy + r * ld_dy + q * 4) = o;
         csum = f4_add(csum, o);
     }
@@ -651,356 +682,20 @@ struct SmallFwdArgs {
     int ld_z, relu, pool, tx_n;
 };
 
-// Exchange: what happens to the block's column sums before they become statistics -- nothing on one GPU (SmallNoExchange), the
-// peer-to-peer exchange over the ranks of the node (SmallP2PExchange: one channel quad per block, tx_n = 1)
+// Exchange: what happens to the block's column sums before they become statistics (forward) or the two means of the data
+// gradient (backward) -- nothing on one GPU (SmallNoExchange), the peer-to-peer exchange over the ranks of the node
+// (SmallP2PExchange: one channel quad per block, tx_n = 1, 256 threads)
 struct SmallNoExchange {
     __device__ __forceinline__ int world_size() const { return 1; }
     __device__ __forceinline__ void all_ranks(float4&, float4&, int, int) const {}
     __device__ __forceinline__ void finish() const {}
 };
 
-template <class Exchange>
-__device__ __forceinline__ void bn_small_fwd_body(const SmallFwdArgs& a, const Exchange& xch) {
-    __shared__ float4 red0[1024], red1[1024];
-    const int tx_n = a.tx_n, ty_n = blockDim.x / tx_n;
-    const int tx = threadIdx.x % tx_n, ty = threadIdx.x / tx_n;
-    const int nv = a.ld_y / 4, q = blockIdx.x * tx_n + tx;
-    const bool qok = q < nv;
-    const int rows = a.N * a.H * a.W, rem = a.C - q * 4;
-    float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
-    if (qok) {
-        if (a.ws) {
-            const float4 bv = a.bias ? ld4_guard(a.bias, q, a.C) : make_float4(0.f, 0.f, 0.f, 0.f);
-            const int Hl = a.H >> 1, Wl = a.W >> 1;
-            const long Mlow = (long)a.N * Hl * Wl, prows = a.phases > 1 ? 4 * Mlow : (long)rows;
-            for (int r = ty; r < rows; r += ty_n) {
-                long pr = r;
-                if (a.phases > 1) {          // output pixel (n, Y, X) <- row (n, Y>>1, X>>1) of phase 2 (Y&1) + (X&1)
-                    const int X = r % a.W, t = r / a.W, Y = t % a.H, n = t / a.H;
-                    pr = (long)((Y & 1) * 2 + (X & 1)) * Mlow + ((long)n * Hl + (Y >> 1)) * Wl + (X >> 1);
-                }
-                // the splits are added in order, but eight (then four) partials are fetched before the first add: with one
-                // block per channel quad there is a single wave per SIMD, and a load -> add chain over 8 ... 32 splits was
-                // the whole kernel (23 us for 512 rows)
-                float4 v = bv;
-                const float* wp = a.ws + pr * a.ldw + q * 4;
-                const long sstride = prows * a.ldw;
-                int sp = 0;
-                for (; sp + 8 <= a.splits; sp += 8) {
-                    float4 l[8];
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) l[e] = *reinterpret_cast<const float4*>(wp + (long)(sp + e) * sstride);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v = f4_add(v, l[e]);
-                }
-                if (sp + 4 <= a.splits) {
-                    float4 l[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) l[e] = *reinterpret_cast<const float4*>(wp + (long)(sp + e) * sstride);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v = f4_add(v, l[e]);
-                    sp += 4;
-                }
-                for (; sp < a.splits; ++sp) v = f4_add(v, *reinterpret_cast<const float4*>(wp + (long)sp * sstride));
-                if (rem < 4) {               // columns beyond Cout hold the results of clamped weight rows
-                    if (rem < 2) v.y = 0.f;
-                    if (rem < 3) v.z = 0.f;
-                    v.w = 0.f;
-                    if (rem < 1) v.x = 0.f;
-                }
-                *reinterpret_cast<float4*>(a.y + (long)r * a.ld_y + q * 4) = v;
-                s1 = f4_add(s1, v);
-                s2 = f4_fma(v, v, s2);
-            }
-        } else {
-            for (int r = ty; r < rows; r += ty_n) {
-                const float4 v = *reinterpret_cast<const float4*>(a.y + (long)r * a.ld_y + q * 4);
-                s1 = f4_add(s1, v);
-                s2 = f4_fma(v, v, s2);
-            }
-        }
-    }
-    small_tree_sum2(red0, red1, s1, s2, tx_n, ty_n, tx, ty);       // also orders the y writes of the block before the reads below
-    xch.all_ranks(s1, s2, q, a.C);                                 // (several ranks: the sums over all of them, in rank order)
-    const double count = (double)rows * xch.world_size();
-    float mq[4], sq[4], iq[4];
-    const float t1[4] = {s1.x, s1.y, s1.z, s1.w}, t2[4] = {s2.x, s2.y, s2.z, s2.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int c = q * 4 + e;
-        const double m = (double)t1[e] / count;
-        double v = (double)t2[e] / count - m * m;
-        if (v < 0.0) v = 0.0;
-        const float mf = (float)m, is = 1.0f / sqrtf((float)v + a.eps);
-        mq[e] = mf;
-        iq[e] = is;
-        sq[e] = (qok && c < a.C) ? a.gamma[c] * is : 0.f;
-        if (ty == 0 && qok && c < a.C) {
-            a.mean[c] = mf;
-            a.invstd[c] = is;
-            a.scale[c] = sq[e];
-            const float unbiased = (float)(v * count / (count - 1.0));
-            a.running_mean[c] = (1.f - a.momentum) * a.running_mean[c] + a.momentum * mf;
-            a.running_var[c] = (1.f - a.momentum) * a.running_var[c] + a.momentum * unbiased;
-        }
-    }
-    if (!qok) {
-        xch.finish();
-        return;
-    }
-    const float4 be = ld4_guard(a.beta, q, a.C);
-    const float slope = a.relu ? 0.f : -1.f;
-    const float4 m = make_float4(mq[0], mq[1], mq[2], mq[3]), sc = make_float4(sq[0], sq[1], sq[2], sq[3]);
-    if (a.pool) {
-        const int Ho = a.H / 2, Wo = a.W / 2, orows = a.N * Ho * Wo;
-        for (int p = ty; p < orows; p += ty_n) {
-            const int wo = p % Wo, t = p / Wo, ho = t % Ho, n = t / Ho;
-            const float* yb = a.y + (((long)n * a.H + 2 * ho) * a.W + 2 * wo) * a.ld_y + q * 4;
-            float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-                for (int dx = 0; dx < 2; ++dx) {
-                    const float4 v = *reinterpret_cast<const float4*>(yb + ((long)dy * a.W + dx) * a.ld_y);
-                    o.x += act_apply(fmaf(v.x - m.x, sc.x, be.x), slope);
-                    o.y += act_apply(fmaf(v.y - m.y, sc.y, be.y), slope);
-                    o.z += act_apply(fmaf(v.z - m.z, sc.z, be.z), slope);
-                    o.w += act_apply(fmaf(v.w - m.w, sc.w, be.w), slope);
-                }
-            *reinterpret_cast<float4*>(a.z + (long)p * a.ld_z + q * 4) = make_float4(o.x * 0.25f, o.y * 0.25f, o.z * 0.25f, o.w * 0.25f);
-        }
-    } else {
-        for (int r = ty; r < rows; r += ty_n) {
-            const float4 v = *reinterpret_cast<const float4*>(a.y + (long)r * a.ld_y + q * 4);
-            float4 o;
-            o.x = act_apply(fmaf(v.x - m.x, sc.x, be.x), slope);
-            o.y = act_apply(fmaf(v.y - m.y, sc.y, be.y), slope);
-            o.z = act_apply(fmaf(v.z - m.z, sc.z, be.z), slope);
-            o.w = act_apply(fmaf(v.w - m.w, sc.w, be.w), slope);
-            *reinterpret_cast<float4*>(a.z + (long)r * a.ld_z + q * 4) = o;
-        }
-    }
-    xch.finish();
-}
-
-__global__ void __launch_bounds__(1024) bn_small_fwd_kernel(SmallFwdArgs a) { bn_small_fwd_body(a, SmallNoExchange()); }
-
-// Evaluation-mode norm layer straight from the split-K partials of the convolution in front (MNK_CONV_DEFER_SPLITK): sums the
-// partials, adds the bias, applies the running-statistics affine + ReLU (+ 2x2 average pool) and writes z -- one launch instead of
-// split reduction + apply, and y never exists.  The reference's per-frame evaluation loops (reconstruction.py:45-62, batch 1) run
-// every convolution split along K, so this is one launch less per norm layer of a frame.  Arithmetic = what the two launches do,
-// bit for bit: the splits in conv3x3_splitk_reduce_stats_kernel's order (four interleaved groups, (g0 + g1) + (g2 + g3), then
-// the bias), then bn_act_fwd_kernel's fmaf / activation / pooling order.
-struct EvalSplitArgs {
-    const float* ws;       // [split][phase][M][ldw]
-    int splits, ldw, phases;
-    const float *bias, *mean, *scale, *beta;
-    float* z;
-    int ld_z, N, H, W, C;  // (H, W): the size of the convolution's output (the up-sampled size for the sub-pixel form)
-    int relu, pool, tx_n, ty_n;
-};
-
-__device__ __forceinline__ float4 eval_split_pixel(const EvalSplitArgs& a, int n, int Y, int X, int q, float4 bv, int rem) {
-    long pr, prows;
-    if (a.phases > 1) {          // output pixel (n, Y, X) <- row (n, Y>>1, X>>1) of phase 2 (Y&1) + (X&1)
-        const int Hl = a.H >> 1, Wl = a.W >> 1;
-        const long Mlow = (long)a.N * Hl * Wl;
-        prows = 4 * Mlow;
-        pr = (long)((Y & 1) * 2 + (X & 1)) * Mlow + ((long)n * Hl + (Y >> 1)) * Wl + (X >> 1);
-    } else {
-        prows = (long)a.N * a.H * a.W;
-        pr = ((long)n * a.H + Y) * a.W + X;
-    }
-    const float* p = a.ws + pr * a.ldw + q * 4;
-    const long sstride = prows * a.ldw;
-    float4 g[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) g[e] = make_float4(0.f, 0.f, 0.f, 0.f);
-    int s = 0;
-    for (; s + 4 <= a.splits; s += 4) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) g[e] = f4_add(g[e], *reinterpret_cast<const float4*>(p + (long)(s + e) * sstride));
-    }
-#pragma unroll
-    for (int e = 0; e < 3; ++e)
-        if (s + e < a.splits) g[e] = f4_add(g[e], *reinterpret_cast<const float4*>(p + (long)(s + e) * sstride));
-    float4 r;
-    r.x = (g[0].x + g[1].x) + (g[2].x + g[3].x);
-    r.y = (g[0].y + g[1].y) + (g[2].y + g[3].y);
-    r.z = (g[0].z + g[1].z) + (g[2].z + g[3].z);
-    r.w = (g[0].w + g[1].w) + (g[2].w + g[3].w);
-    if (a.bias) r = f4_add(r, bv);
-    r.x = rem > 0 ? r.x : 0.f;   // columns beyond Cout hold the results of clamped weight rows
-    r.y = rem > 1 ? r.y : 0.f;
-    r.z = rem > 2 ? r.z : 0.f;
-    r.w = rem > 3 ? r.w : 0.f;
-    return r;
-}
-
-__global__ void __launch_bounds__(256) bn_eval_split_fwd_kernel(EvalSplitArgs a) {
-    const int tx = threadIdx.x % a.tx_n, ty = threadIdx.x / a.tx_n;
-    const int nv = a.ld_z / 4, q = blockIdx.x * a.tx_n + tx;
-    if (q >= nv || ty >= a.ty_n) return;
-    const int Ho = a.pool ? a.H / 2 : a.H, Wo = a.pool ? a.W / 2 : a.W;
-    const int orows = a.N * Ho * Wo;
-    const int p = blockIdx.y * a.ty_n + ty;
-    if (p >= orows) return;
-    const int rem = a.C - q * 4;
-    const float4 bv = a.bias ? ld4_guard(a.bias, q, a.C) : make_float4(0.f, 0.f, 0.f, 0.f);
-    const float4 m = ld4_guard(a.mean, q, a.C), sc = ld4_guard(a.scale, q, a.C), be = ld4_guard(a.beta, q, a.C);
-    const float slope = a.relu ? 0.f : -1.f;
-    const int wo = p % Wo, t = p / Wo, ho = t % Ho, n = t / Ho;
-    float4 o;
-    if (a.pool) {
-        float4 v[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = eval_split_pixel(a, n, 2 * ho + (k >> 1), 2 * wo + (k & 1), q, bv, rem);
-        o = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            o.x += act_apply(fmaf(v[k].x - m.x, sc.x, be.x), slope);
-            o.y += act_apply(fmaf(v[k].y - m.y, sc.y, be.y), slope);
-            o.z += act_apply(fmaf(v[k].z - m.z, sc.z, be.z), slope);
-            o.w += act_apply(fmaf(v[k].w - m.w, sc.w, be.w), slope);
-        }
-        o.x *= 0.25f;
-        o.y *= 0.25f;
-        o.z *= 0.25f;
-        o.w *= 0.25f;
-    } else {
-        const float4 v = eval_split_pixel(a, n, ho, wo, q, bv, rem);
-        o.x = act_apply(fmaf(v.x - m.x, sc.x, be.x), slope);
-        o.y = act_apply(fmaf(v.y - m.y, sc.y, be.y), slope);
-        o.z = act_apply(fmaf(v.z - m.z, sc.z, be.z), slope);
-        o.w = act_apply(fmaf(v.w - m.w, sc.w, be.w), slope);
-    }
-    *reinterpret_cast<float4*>(a.z + (long)p * a.ld_z + q * 4) = o;      // guarded parameter loads make the pad lanes zero
-}
-
-__global__ void __launch_bounds__(1024) bn_small_bwd_kernel(BwdLoader L, double count, int rows, int nv, int tx_n,
-                                                            float* __restrict__ sums, float* __restrict__ dy, int ld_dy) {
-    __shared__ float4 red0[1024], red1[1024];
-    const int ty_n = blockDim.x / tx_n;
-    const int tx = threadIdx.x % tx_n, ty = threadIdx.x / tx_n;
-    const int q = blockIdx.x * tx_n + tx;
-    const bool qok = q < nv;
-    float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
-    BwdLoader::State st;
-    L.init(st);
-    if (qok)
-        for (int r = ty; r < rows; r += ty_n) {
-            float4 g, xh;
-            L.load(r, q, st, g, xh);
-            a = f4_add(a, g);
-            b = f4_fma(g, xh, b);
-        }
-    small_tree_sum2(red0, red1, a, b, tx_n, ty_n, tx, ty);
-    if (!qok) return;
-    const int C = L.C, rem = C - q * 4;
-    if (ty == 0) {                         // dbeta = sum g, dgamma = sum g * xhat
-        const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (q * 4 + e < C) {
-                sums[q * 4 + e] = av[e];
-                sums[C + q * 4 + e] = bv[e];
-            }
-    }
-    const float inv = (float)(1.0 / count);
-    const float4 k1 = make_float4(a.x * inv, a.y * inv, a.z * inv, a.w * inv), k2 = make_float4(b.x * inv, b.y * inv, b.z * inv, b.w * inv);
-    const float4 sc = ld4_guard(L.scale, q, C);
-    for (int r = ty; r < rows; r += ty_n) {
-        float4 g, xh;
-        L.load(r, q, st, g, xh);
-        float4 o;
-        o.x = sc.x * (g.x - k1.x - xh.x * k2.x);
-        o.y = sc.y * (g.y - k1.y - xh.y * k2.y);
-        o.z = sc.z * (g.z - k1.z - xh.z * k2.z);
-        o.w = sc.w * (g.w - k1.w - xh.w * k2.w);
-        if (rem < 4) {  // keep pad channels of dy at zero
-            if (rem < 2) o.y = 0.f;
-            if (rem < 3) o.z = 0.f;
-            o.w = 0.f;
-        }
-        *reinterpret_cast<float4*>(dy + (long)r * ld_dy + q * 4) = o;
-    }
-}
-
-// bn_small_bwd_kernel of one rank of a data-parallel run: ONE channel quad per block (256 threads over the rows); after the
-// block's own sums (= this rank's dbeta / dgamma contributions, written to `sums`) wave 0 exchanges the eight of them with every
-// rank of the node in one round trip (p2p_exchange_values) and the apply pass runs with the sums over all ranks -- statistics,
-// exchange and apply of a small layer in one launch, as on a single GPU (count = rows of ALL ranks).
-__global__ void __launch_bounds__(256) bn_small_bwd_sync_kernel(BwdLoader L, double count, int rows, int nv, float* __restrict__ sums,
-                                                                float* __restrict__ dy, int ld_dy, PeerTable peers, int rank,
-                                                                int world, unsigned* state, unsigned long long timeout_ticks) {
-    __shared__ float4 red0[256], red1[256];
-    __shared__ float glob[8];
-    const int ty = threadIdx.x, q = blockIdx.x;          // (tx_n = 1: q < nv for every block)
-    const unsigned seq = state[0] + 1;
-    const int slot = (int)(seq % P2P_SLOTS);
-    float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
-    BwdLoader::State st;
-    L.init(st);
-    for (int r = ty; r < rows; r += 256) {
-        float4 g, xh;
-        L.load(r, q, st, g, xh);
-        a = f4_add(a, g);
-        b = f4_fma(g, xh, b);
-    }
-    small_tree_sum2(red0, red1, a, b, 1, 256, 0, ty);
-    const int C = L.C, rem = C - q * 4;
-    const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
-    if (ty == 0) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (q * 4 + e < C) {
-                sums[q * 4 + e] = av[e];
-                sums[C + q * 4 + e] = bv[e];
-            }
-    }
-    if (ty < 64) {                                         // wave 0: value j = lane / W of {a.xyzw, b.xyzw}
-        const int W = world <= 8 ? 8 : 16, per = 64 / W;
-        for (int j0 = 0; j0 < 8; j0 += per) {
-            const int j = j0 + ty / W, e = j & 3, c = q * 4 + e;
-            float v = 0.f;
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (e == k) v = j < 4 ? av[k] : bv[k];
-            const int index = (j < 8 && c < C) ? (j < 4 ? c : C + c) : -1;
-            const float all = p2p_exchange_values(peers, rank, world, slot, seq, index, v, state, timeout_ticks);
-            if ((ty & (W - 1)) == 0 && j < 8) glob[j] = all;
-        }
-    }
-    __syncthreads();
-    const float inv = (float)(1.0 / count);
-    const float4 k1 = make_float4(glob[0] * inv, glob[1] * inv, glob[2] * inv, glob[3] * inv),
-                 k2 = make_float4(glob[4] * inv, glob[5] * inv, glob[6] * inv, glob[7] * inv);
-    const float4 sc = ld4_guard(L.scale, q, C);
-    for (int r = ty; r < rows; r += 256) {
-        float4 g, xh;
-        L.load(r, q, st, g, xh);
-        float4 o;
-        o.x = sc.x * (g.x - k1.x - xh.x * k2.x);
-        o.y = sc.y * (g.y - k1.y - xh.y * k2.y);
-        o.z = sc.z * (g.z - k1.z - xh.z * k2.z);
-        o.w = sc.w * (g.w - k1.w - xh.w * k2.w);
-        if (rem < 4) {  // keep pad channels of dy at zero
-            if (rem < 2) o.y = 0.f;
-            if (rem < 3) o.z = 0.f;
-            o.w = 0.f;
-        }
-        *reinterpret_cast<float4*>(dy + (long)r * ld_dy + q * 4) = o;
-    }
-    p2p_finish_launch(state, seq);
-}
-
-// bn_small_fwd_kernel of one rank of a data-parallel run (the forward twin of the kernel above, round 5): ONE channel quad per
-// block; after the block's tree sum wave 0 exchanges the quad's eight sums (sum, sum of squares of four channels) with every rank
-// of the node in one round trip, and the statistics, the running statistics and the apply pass are made from the sums over ALL
-// ranks (count = rows * world) -- split-K reduction, statistics, exchange, finalisation and apply of a small layer in one
-// launch, as on a single GPU.  Replaces sync_batchnorm/batchnorm.py:55-78 (+ the reduce / broadcast of :95-111) for these layers.
+// One rank of a data-parallel run: after the block's tree sum wave 0 exchanges the quad's eight sums (two sums of four channels)
+// with every rank of the node in one round trip (p2p_exchange_values), and the rest of the launch runs with the sums over ALL
+// ranks.  Replaces sync_batchnorm/batchnorm.py:55-78 (+ the reduce / broadcast of :95-111) for the small layers.
 struct SmallP2PExchange {
-    PeerTable peers;
+    const PeerTable& peers;        // the kernel's own argument: a copy would be indexed per lane and so live in private memory
     int rank, world;
     unsigned* state;
     unsigned long long timeout_ticks;
@@ -1030,10 +725,241 @@ struct SmallP2PExchange {
     __device__ __forceinline__ void finish() const { p2p_finish_launch(state, seq); }
 };
 
+// Row of output pixel (n, Y, X) of an N x H x W map in one split's partials [phase][M][ldw] (every split holds N * H * W rows).
+// phases == 4, the sub-pixel form of an up-sampled convolution: row (n, Y>>1, X>>1) of phase 2 (Y&1) + (X&1)
+__device__ __forceinline__ long split_partial_row(int phases, int N, int H, int W, int n, int Y, int X) {
+    if (phases > 1) {
+        const int Hl = H >> 1, Wl = W >> 1;
+        const long Mlow = (long)N * Hl * Wl;
+        return (long)((Y & 1) * 2 + (X & 1)) * Mlow + ((long)n * Hl + (Y >> 1)) * Wl + (X >> 1);
+    }
+    return ((long)n * H + Y) * W + X;
+}
+
+// CAP: threads per block at most (the tree sum's LDS)
+template <int CAP, class Exchange>
+__device__ __forceinline__ void bn_small_fwd_body(const SmallFwdArgs& a, const Exchange& xch) {
+    __shared__ float4 red0[CAP], red1[CAP];
+    const int tx_n = a.tx_n, ty_n = blockDim.x / tx_n;
+    const int tx = threadIdx.x % tx_n, ty = threadIdx.x / tx_n;
+    const int nv = a.ld_y / 4, q = blockIdx.x * tx_n + tx;
+    const bool qok = q < nv;
+    const int rows = a.N * a.H * a.W, rem = a.C - q * 4;
+    float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
+    if (qok) {
+        if (a.ws) {
+            const float4 bv = a.bias ? ld4_guard(a.bias, q, a.C) : make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int r = ty; r < rows; r += ty_n) {
+                long pr = r;                 // (one phase: the partials have y's own rows)
+                if (a.phases > 1) {
+                    const int X = r % a.W, t = r / a.W, Y = t % a.H, n = t / a.H;
+                    pr = split_partial_row(a.phases, a.N, a.H, a.W, n, Y, X);
+                }
+                // the splits are added in order, but eight (then four) partials are fetched before the first add: with one
+                // block per channel quad there is a single wave per SIMD, and a load -> add chain over 8 ... 32 splits was
+                // the whole kernel (23 us for 512 rows)
+                float4 v = bv;
+                const float* wp = a.ws + pr * a.ldw + q * 4;
+                const long sstride = (long)rows * a.ldw;
+                int sp = 0;
+                for (; sp + 8 <= a.splits; sp += 8) {
+                    float4 l[8];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) l[e] = *reinterpret_cast<const float4*>(wp + (long)(sp + e) * sstride);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) v = f4_add(v, l[e]);
+                }
+                if (sp + 4 <= a.splits) {
+                    float4 l[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) l[e] = *reinterpret_cast<const float4*>(wp + (long)(sp + e) * sstride);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v = f4_add(v, l[e]);
+                    sp += 4;
+                }
+                for (; sp < a.splits; ++sp) v = f4_add(v, *reinterpret_cast<const float4*>(wp + (long)sp * sstride));
+                zero_pad_lanes(v, rem);      // columns beyond Cout hold the results of clamped weight rows
+                *reinterpret_cast<float4*>(a.y + (long)r * a.ld_y + q * 4) = v;
+                s1 = f4_add(s1, v);
+                s2 = f4_fma(v, v, s2);
+            }
+        } else {
+            for (int r = ty; r < rows; r += ty_n) {
+                const float4 v = *reinterpret_cast<const float4*>(a.y + (long)r * a.ld_y + q * 4);
+                s1 = f4_add(s1, v);
+                s2 = f4_fma(v, v, s2);
+            }
+        }
+    }
+    small_tree_sum2(red0, red1, s1, s2, tx_n, ty_n, tx, ty);       // also orders the y writes of the block before the reads below
+    xch.all_ranks(s1, s2, q, a.C);                                 // (several ranks: the sums over all of them, in rank order)
+    const double count = (double)rows * xch.world_size();
+    float mq[4], sq[4];
+    const float t1[4] = {s1.x, s1.y, s1.z, s1.w}, t2[4] = {s2.x, s2.y, s2.z, s2.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int c = q * 4 + e;
+        const BnStats st = bn_finalize(t1[e], t2[e], count, a.eps);
+        mq[e] = st.mean;
+        sq[e] = (qok && c < a.C) ? a.gamma[c] * st.invstd : 0.f;
+        if (ty == 0 && qok && c < a.C) {
+            a.mean[c] = st.mean;
+            a.invstd[c] = st.invstd;
+            a.scale[c] = sq[e];
+            bn_update_running(a.running_mean, a.running_var, c, a.momentum, st, count);
+        }
+    }
+    if (!qok) {
+        xch.finish();
+        return;
+    }
+    const float4 be = ld4_guard(a.beta, q, a.C);
+    const float slope = a.relu ? 0.f : -1.f;
+    const float4 m = make_float4(mq[0], mq[1], mq[2], mq[3]), sc = make_float4(sq[0], sq[1], sq[2], sq[3]);
+    if (a.pool) {
+        const int Ho = a.H / 2, Wo = a.W / 2, orows = a.N * Ho * Wo;
+        for (int p = ty; p < orows; p += ty_n) {
+            const int wo = p % Wo, t = p / Wo, ho = t % Ho, n = t / Ho;
+            const float* yb = a.y + (((long)n * a.H + 2 * ho) * a.W + 2 * wo) * a.ld_y + q * 4;
+            *reinterpret_cast<float4*>(a.z + (long)p * a.ld_z + q * 4) =
+                bn_apply4_pool([=](int dy, int dx) { return ld4_window(yb, a.W, a.ld_y, dy, dx); }, m, sc, be, slope);
+        }
+    } else {
+        for (int r = ty; r < rows; r += ty_n)
+            *reinterpret_cast<float4*>(a.z + (long)r * a.ld_z + q * 4) =
+                bn_apply4(*reinterpret_cast<const float4*>(a.y + (long)r * a.ld_y + q * 4), m, sc, be, slope);
+    }
+    xch.finish();
+}
+
+__global__ void __launch_bounds__(1024) bn_small_fwd_kernel(SmallFwdArgs a) { bn_small_fwd_body<1024>(a, SmallNoExchange()); }
+
+// split-K reduction, statistics, exchange, finalisation and apply of a small layer of one rank of several in one launch, as on a
+// single GPU (count = rows * world)
 __global__ void __launch_bounds__(256) bn_small_fwd_sync_kernel(SmallFwdArgs a, PeerTable peers, int rank, int world, unsigned* state,
                                                                 unsigned long long timeout_ticks) {
-    SmallP2PExchange x{peers, rank, world, state, timeout_ticks, state[0] + 1};
-    bn_small_fwd_body(a, x);
+    bn_small_fwd_body<256>(a, SmallP2PExchange{peers, rank, world, state, timeout_ticks, state[0] + 1});
+}
+
+// The whole backward pass of a small layer: the block's own sums (= this rank's dbeta / dgamma contributions, written to `sums`),
+// their exchange, and the apply pass with the sums over all ranks (count = rows of ALL ranks).
+template <int CAP, class Exchange>
+__device__ __forceinline__ void bn_small_bwd_body(const BwdLoader& L, double count, int rows, int nv, int tx_n, float* __restrict__ sums,
+                                                  float* __restrict__ dy, int ld_dy, const Exchange& xch) {
+    __shared__ float4 red0[CAP], red1[CAP];
+    const int ty_n = blockDim.x / tx_n;
+    const int tx = threadIdx.x % tx_n, ty = threadIdx.x / tx_n;
+    const int q = blockIdx.x * tx_n + tx;
+    const bool qok = q < nv;
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
+    BwdLoader::State st;
+    L.init(st);
+    if (qok)
+        for (int r = ty; r < rows; r += ty_n) {
+            float4 g, xh;
+            L.load(r, q, st, g, xh);
+            a = f4_add(a, g);
+            b = f4_fma(g, xh, b);
+        }
+    small_tree_sum2(red0, red1, a, b, tx_n, ty_n, tx, ty);
+    const int C = L.C;
+    if (ty == 0 && qok) {                  // dbeta = sum g, dgamma = sum g * xhat
+        const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (q * 4 + e < C) {
+                sums[q * 4 + e] = av[e];
+                sums[C + q * 4 + e] = bv[e];
+            }
+    }
+    xch.all_ranks(a, b, q, C);
+    if (!qok) {
+        xch.finish();
+        return;
+    }
+    const float inv = (float)(1.0 / count);
+    const float4 k1 = f4_scale(a, inv), k2 = f4_scale(b, inv);
+    const float4 sc = ld4_guard(L.scale, q, C);
+    for (int r = ty; r < rows; r += ty_n) {
+        float4 g, xh;
+        L.load(r, q, st, g, xh);
+        float4 o = bn_dx4(g, xh, sc, k1, k2);
+        zero_pad_lanes(o, C - q * 4);       // keep pad channels of dy at zero
+        *reinterpret_cast<float4*>(dy + (long)r * ld_dy + q * 4) = o;
+    }
+    xch.finish();
+}
+
+__global__ void __launch_bounds__(1024) bn_small_bwd_kernel(BwdLoader L, double count, int rows, int nv, int tx_n,
+                                                            float* __restrict__ sums, float* __restrict__ dy, int ld_dy) {
+    bn_small_bwd_body<1024>(L, count, rows, nv, tx_n, sums, dy, ld_dy, SmallNoExchange());
+}
+
+__global__ void __launch_bounds__(256) bn_small_bwd_sync_kernel(BwdLoader L, double count, int rows, int nv, float* __restrict__ sums,
+                                                                float* __restrict__ dy, int ld_dy, PeerTable peers, int rank,
+                                                                int world, unsigned* state, unsigned long long timeout_ticks) {
+    bn_small_bwd_body<256>(L, count, rows, nv, 1, sums, dy, ld_dy,
+                           SmallP2PExchange{peers, rank, world, state, timeout_ticks, state[0] + 1});
+}
+
+// Evaluation-mode norm layer straight from the split-K partials of the convolution in front (MNK_CONV_DEFER_SPLITK): sums the
+// partials, adds the bias, applies the running-statistics affine + ReLU (+ 2x2 average pool) and writes z -- one launch instead of
+// split reduction + apply, and y never exists.  The reference's per-frame evaluation loops (reconstruction.py:45-62, batch 1) run
+// every convolution split along K, so this is one launch less per norm layer of a frame.  Arithmetic = what the two launches do,
+// bit for bit: the splits in conv3x3_splitk_reduce_stats_kernel's order (four interleaved groups, (g0 + g1) + (g2 + g3), then
+// the bias), then bn_act_fwd_kernel's fmaf / activation / pooling order.
+struct EvalSplitArgs {
+    const float* ws;       // [split][phase][M][ldw]
+    int splits, ldw, phases;
+    const float *bias, *mean, *scale, *beta;
+    float* z;
+    int ld_z, N, H, W, C;  // (H, W): the size of the convolution's output (the up-sampled size for the sub-pixel form)
+    int relu, pool, tx_n, ty_n;
+};
+
+__device__ __forceinline__ float4 eval_split_pixel(const EvalSplitArgs& a, int n, int Y, int X, int q, float4 bv, int rem) {
+    const float* p = a.ws + split_partial_row(a.phases, a.N, a.H, a.W, n, Y, X) * a.ldw + q * 4;
+    const long sstride = (long)a.N * a.H * a.W * a.ldw;
+    float4 g[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) g[e] = make_float4(0.f, 0.f, 0.f, 0.f);
+    int s = 0;
+    for (; s + 4 <= a.splits; s += 4) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) g[e] = f4_add(g[e], *reinterpret_cast<const float4*>(p + (long)(s + e) * sstride));
+    }
+#pragma unroll
+    for (int e = 0; e < 3; ++e)
+        if (s + e < a.splits) g[e] = f4_add(g[e], *reinterpret_cast<const float4*>(p + (long)(s + e) * sstride));
+    float4 r = f4_add(f4_add(g[0], g[1]), f4_add(g[2], g[3]));
+    if (a.bias) r = f4_add(r, bv);
+    zero_pad_lanes(r, rem);      // columns beyond Cout hold the results of clamped weight rows
+    return r;
+}
+
+__global__ void __launch_bounds__(256) bn_eval_split_fwd_kernel(EvalSplitArgs a) {
+    const int tx = threadIdx.x % a.tx_n, ty = threadIdx.x / a.tx_n;
+    const int nv = a.ld_z / 4, q = blockIdx.x * a.tx_n + tx;
+    if (q >= nv || ty >= a.ty_n) return;
+    const int Ho = a.pool ? a.H / 2 : a.H, Wo = a.pool ? a.W / 2 : a.W;
+    const int orows = a.N * Ho * Wo;
+    const int p = blockIdx.y * a.ty_n + ty;
+    if (p >= orows) return;
+    const int rem = a.C - q * 4;
+    const float4 bv = a.bias ? ld4_guard(a.bias, q, a.C) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 m = ld4_guard(a.mean, q, a.C), sc = ld4_guard(a.scale, q, a.C), be = ld4_guard(a.beta, q, a.C);
+    const float slope = a.relu ? 0.f : -1.f;
+    const int wo = p % Wo, t = p / Wo, ho = t % Ho, n = t / Ho;
+    float4 o;
+    if (a.pool) {
+        float4 v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = eval_split_pixel(a, n, 2 * ho + (k >> 1), 2 * wo + (k & 1), q, bv, rem);
+        o = bn_apply4_pool([&](int dy, int dx) { return v[dy * 2 + dx]; }, m, sc, be, slope);
+    } else {
+        o = bn_apply4(eval_split_pixel(a, n, ho, wo, q, bv, rem), m, sc, be, slope);
+    }
+    *reinterpret_cast<float4*>(a.z + (long)p * a.ld_z + q * 4) = o;      // guarded parameter loads make the pad lanes zero
 }
 
 static inline int small_txn(int nv) { return g_small_txn ? g_small_txn : (nv >= 128 ? 4 : (nv >= 64 ? 2 : 1)); }
@@ -1048,10 +974,83 @@ static inline void small_shape(int nv, int* threads, int* tx_n) {
     *threads = (g_small_fwd_threads == 512 || g_small_fwd_threads == 1024) ? g_small_fwd_threads : 256;
 }
 
+// The first stage of a column-sum pair over `frames` x `rows` rows of leading dimension ld, for entry point `who`: its thread map,
+// once the workspace ([frame][row block][2][ld]) is known to hold it ...
+static int partials_map(const char* who, long rows, int frames, int ld, size_t ws_floats, Map2D* m) {
+    *m = make_map(rows, ld);
+    if (ws_floats < (size_t)frames * m->row_blocks * 2 * ld) {
+        set_error("%s: workspace too small", who);
+        return MNK_EWORKSPACE;
+    }
+    return MNK_OK;
+}
+// ... and its launch; the second stage reads m.row_blocks partials per frame
+template <class Loader>
+static void launch_partials(const Loader& L, const Map2D& m, long rows, int frames, int ld, float* ws, hipStream_t s) {
+    hipLaunchKernelGGL(colsum2_partial_kernel<Loader>, dim3(m.col_tiles, m.row_blocks, frames), dim3(256), 0, s, L, rows, ld / 4,
+                       ld, m.tx, m.ty, m.rows_per_block, ws);
+}
+
 static inline int grid_for(long total, int cap = 2048) {
     long b = (total + 255) / 256;
     if (b < 1) b = 1;
     return (int)(b < cap ? b : cap);
+}
+
+// ---- the one-launch forms of a small layer, plain and as one rank of several --------------------------------------------------
+// p2p: the exchange handle of one rank of several (the *_sync entry points: filled into a P2PLaunch once the arguments are checked,
+// as those entry points always did), or NULL
+static int small_fwd(const char* who, void* p2p, int timeout_ms, const float* ws, int splits, int ldw, int phases, const float* bias, float* y,
+                     int ld_y, int N, int H, int W, int C, const float* gamma, const float* beta, float* running_mean,
+                     float* running_var, float momentum, float eps, float* mean, float* invstd, float* scale, float* z, int ld_z,
+                     int relu, int pool, hipStream_t s) {
+    MNK_REQUIRE_FOR(who, y && gamma && beta && running_mean && running_var && mean && invstd && scale && z && N > 0 && H > 0 && W > 0);
+    MNK_REQUIRE_FOR(who, C > 0 && ld_y % 4 == 0 && ld_y == round_up(C, 4) && ld_z == ld_y && (long)N * H * W <= 4096);
+    MNK_REQUIRE_FOR(who, !ws || (splits >= 1 && ldw == ld_y && (phases == 1 || (phases == 4 && H % 2 == 0 && W % 2 == 0))));
+    MNK_REQUIRE_FOR(who, !pool || (H % 2 == 0 && W % 2 == 0));
+    P2PLaunch pl;
+    const int rc = p2p ? p2p_launch(who, p2p, C, timeout_ms, &pl) : MNK_OK;
+    if (rc != MNK_OK) return rc;
+    ProfScope prof(K_BN_APPLY, s, (double)N * H * W * C * 4 * 3.0);
+    SmallFwdArgs a{ws, splits, ldw, phases, bias, y, ld_y, N, H, W, C, gamma, beta, running_mean, running_var, momentum, eps,
+                   mean, invstd, scale, z, ld_z, relu, pool, 1};
+    if (p2p) {
+        hipLaunchKernelGGL(bn_small_fwd_sync_kernel, dim3(ld_y / 4), dim3(256), 0, s, a, pl.peers, pl.rank, pl.world, pl.state,
+                           pl.timeout_ticks);
+    } else {
+        int threads;
+        small_shape(ld_y / 4, &threads, &a.tx_n);
+        MNK_REQUIRE_FOR(who, a.tx_n >= 1 && a.tx_n <= 64 && (a.tx_n & (a.tx_n - 1)) == 0);
+        hipLaunchKernelGGL(bn_small_fwd_kernel, dim3(ceil_div(ld_y / 4, a.tx_n)), dim3(threads), 0, s, a);
+    }
+    MNK_LAUNCH_CHECK_FOR(who);
+    return MNK_OK;
+}
+
+static int small_bwd(const char* who, void* p2p, int timeout_ms, const float* y, int ld_y, const float* dz, int ld_dz, const float* mean,
+                     const float* invstd, const float* scale, const float* beta, double count, int N, int H, int W, int C, int relu,
+                     int pool, float* sums, float* dy, int ld_dy, hipStream_t s) {
+    MNK_REQUIRE_FOR(who, y && dz && mean && invstd && scale && beta && sums && dy && N > 0 && H > 0 && W > 0 && C > 0 && count > 1);
+    MNK_REQUIRE_FOR(who, ld_y % 4 == 0 && ld_y >= round_up(C, 4) && ld_dy % 4 == 0 && ld_dy >= round_up(C, 4) && ld_dz >= C);
+    MNK_REQUIRE_FOR(who, (long)N * H * W <= 4096 && (!pool || (H % 2 == 0 && W % 2 == 0)));
+    P2PLaunch pl;
+    const int rc = p2p ? p2p_launch(who, p2p, C, timeout_ms, &pl) : MNK_OK;
+    if (rc != MNK_OK) return rc;
+    ProfScope prof(K_BN_BWD, s, (double)N * H * W * C * 4 * 5.0);
+    const int nv = round_up(C, 4) / 4;
+    BwdLoader L{y, dz, mean, invstd, scale, beta, ld_y, ld_dz, 0, H, W, C, pool, 0, relu ? 0.f : -1.f};
+    if (p2p) {
+        hipLaunchKernelGGL(bn_small_bwd_sync_kernel, dim3(nv), dim3(256), 0, s, L, count, N * H * W, nv, sums, dy, ld_dy, pl.peers,
+                           pl.rank, pl.world, pl.state, pl.timeout_ticks);
+    } else {
+        int threads = 256, txn = small_txn(nv);
+        if (g_small_bwd_shape) small_shape(nv, &threads, &txn);
+        MNK_REQUIRE_FOR(who, txn >= 1 && txn <= 64 && (txn & (txn - 1)) == 0);
+        hipLaunchKernelGGL(bn_small_bwd_kernel, dim3(ceil_div(nv, txn)), dim3(threads), 0, s, L, count, N * H * W, nv, txn, sums, dy,
+                           ld_dy);
+    }
+    MNK_LAUNCH_CHECK_FOR(who);
+    return MNK_OK;
 }
 
 }  // namespace
@@ -1068,18 +1067,14 @@ size_t mnk_norm_workspace_floats(long rows_per_frame, int frames, int ld) {
 int mnk_norm_stats(const float* x, int ld, long rows_per_frame, int frames, int C, float* sums, float* ws,
                    size_t ws_floats, void* stream) {
     MNK_REQUIRE(x && sums && ws && rows_per_frame > 0 && frames > 0 && C > 0 && ld % 4 == 0 && ld >= C);
-    Map2D m = make_map(rows_per_frame, ld);
-    if (ws_floats < (size_t)frames * m.row_blocks * 2 * ld) {
-        set_error("mnk_norm_stats: workspace too small");
-        return MNK_EWORKSPACE;
-    }
+    Map2D m;
+    const int rc = partials_map(__func__, rows_per_frame, frames, ld, ws_floats, &m);
+    if (rc != MNK_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(K_BN_STATS, s, (double)rows_per_frame * frames * C * 4);
-    StatsLoader L{x, ld};
-    hipLaunchKernelGGL(colsum2_partial_kernel<StatsLoader>, dim3(m.col_tiles, m.row_blocks, frames), dim3(256), 0, s, L,
-                       rows_per_frame, ld / 4, ld, m.tx, m.ty, m.rows_per_block, ws);
-    hipLaunchKernelGGL(colsum2_final_kernel, dim3(ceil_div(2 * frames * C, 4)), dim3(256), 0, s, ws, m.row_blocks, ld, C,
-                       frames, sums, 2);
+    launch_partials(StatsLoader{x, ld}, m, rows_per_frame, frames, ld, ws, s);
+    hipLaunchKernelGGL(colsum2_final_kernel, dim3(ceil_div(2 * frames * C, 4)), dim3(256), 0, s, ws, m.row_blocks, ld, C, frames,
+                       sums, 2);
     MNK_LAUNCH_CHECK();
     return MNK_OK;
 }
@@ -1128,18 +1123,15 @@ int mnk_norm_act_bwd_stats(const float* y, int ld_y, const float* dz, int ld_dz,
     const int frames = per_frame ? N : 1;
     const long rows = per_frame ? (long)H * W : (long)N * H * W;
     const int ldc = round_up(C, 4);
-    Map2D m = make_map(rows, ldc);
-    if (ws_floats < (size_t)frames * m.row_blocks * 2 * ldc) {
-        set_error("mnk_norm_act_bwd_stats: workspace too small");
-        return MNK_EWORKSPACE;
-    }
+    Map2D m;
+    const int rc = partials_map(__func__, rows, frames, ldc, ws_floats, &m);
+    if (rc != MNK_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(K_BN_BWD, s, (double)N * H * W * C * 4 * (pool ? 1.25 : 2.0));
     BwdLoader L{y, dz, mean, invstd, scale, beta, ld_y, ld_dz, dz_off, H, W, C, pool, per_frame ? C : 0, slope};
-    hipLaunchKernelGGL(colsum2_partial_kernel<BwdLoader>, dim3(m.col_tiles, m.row_blocks, frames), dim3(256), 0, s, L, rows,
-                       ldc / 4, ldc, m.tx, m.ty, m.rows_per_block, ws);
-    hipLaunchKernelGGL(colsum2_final_kernel, dim3(ceil_div(2 * frames * C, 4)), dim3(256), 0, s, ws, m.row_blocks, ldc, C,
-                       frames, sums, 2);
+    launch_partials(L, m, rows, frames, ldc, ws, s);
+    hipLaunchKernelGGL(colsum2_final_kernel, dim3(ceil_div(2 * frames * C, 4)), dim3(256), 0, s, ws, m.row_blocks, ldc, C, frames,
+                       sums, 2);
     MNK_LAUNCH_CHECK();
     return MNK_OK;
 }
@@ -1214,14 +1206,10 @@ int mnk_bn_stats_finalize(const float* x, int ld, long rows, int C, const float*
     const float* partial = pre_partial;
     int row_blocks = pre_row_blocks;
     if (!pre_partial) {
-        Map2D m = make_map(rows, ld);
-        if (ws_floats < (size_t)m.row_blocks * 2 * ld) {
-            set_error("mnk_bn_stats_finalize: workspace too small");
-            return MNK_EWORKSPACE;
-        }
-        StatsLoader L{x, ld};
-        hipLaunchKernelGGL(colsum2_partial_kernel<StatsLoader>, dim3(m.col_tiles, m.row_blocks, 1), dim3(256), 0, s, L, rows,
-                           ld / 4, ld, m.tx, m.ty, m.rows_per_block, ws);
+        Map2D m;
+        const int rc = partials_map(__func__, rows, 1, ld, ws_floats, &m);
+        if (rc != MNK_OK) return rc;
+        launch_partials(StatsLoader{x, ld}, m, rows, 1, ld, ws, s);
         partial = ws;
         row_blocks = m.row_blocks;
     }
@@ -1253,7 +1241,7 @@ int mnk_bn_stats_finish_sync(void* p2p, const float* partial, int row_blocks, in
     MNK_REQUIRE(p2p && partial && sums_global && row_blocks > 0 && C > 0 && ld >= C);
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(K_BN_STATS, s, (double)row_blocks * 2 * C * 4);
-    const int rc = launch_final_sync(p2p, partial, row_blocks, ld, C, sums_local, sums_global, timeout_ms, s);
+    const int rc = launch_final_sync(__func__, p2p, partial, row_blocks, ld, C, sums_local, sums_global, timeout_ms, s);
     if (rc != MNK_OK) return rc;
     MNK_LAUNCH_CHECK();
     return MNK_OK;
@@ -1261,17 +1249,13 @@ int mnk_bn_stats_finish_sync(void* p2p, const float* partial, int row_blocks, in
 int mnk_bn_stats_sync(void* p2p, const float* x, int ld, long rows, int C, float* sums_local, float* sums_global, float* ws,
                       size_t ws_floats, int timeout_ms, void* stream) {
     MNK_REQUIRE(p2p && x && sums_global && ws && rows > 0 && C > 0 && ld % 4 == 0 && ld >= C);
-    Map2D m = make_map(rows, ld);
-    if (ws_floats < (size_t)m.row_blocks * 2 * ld) {
-        set_error("mnk_bn_stats_sync: workspace too small");
-        return MNK_EWORKSPACE;
-    }
+    Map2D m;
+    int rc = partials_map(__func__, rows, 1, ld, ws_floats, &m);
+    if (rc != MNK_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(K_BN_STATS, s, (double)rows * C * 4);
-    StatsLoader L{x, ld};
-    hipLaunchKernelGGL(colsum2_partial_kernel<StatsLoader>, dim3(m.col_tiles, m.row_blocks, 1), dim3(256), 0, s, L, rows, ld / 4, ld,
-                       m.tx, m.ty, m.rows_per_block, ws);
-    const int rc = launch_final_sync(p2p, ws, m.row_blocks, ld, C, sums_local, sums_global, timeout_ms, s);
+    launch_partials(StatsLoader{x, ld}, m, rows, 1, ld, ws, s);
+    rc = launch_final_sync(__func__, p2p, ws, m.row_blocks, ld, C, sums_local, sums_global, timeout_ms, s);
     if (rc != MNK_OK) return rc;
     MNK_LAUNCH_CHECK();
     return MNK_OK;
@@ -1285,17 +1269,14 @@ int mnk_bn_act_bwd_stats_sync(void* p2p, const float* y, int ld_y, const float* 
     MNK_REQUIRE((!pool || (H >= 2 && W >= 2)) && (long)N * H * W < (1L << 31));
     const long rows = (long)N * H * W;
     const int ldc = round_up(C, 4);
-    Map2D m = make_map(rows, ldc);
-    if (ws_floats < (size_t)m.row_blocks * 2 * ldc) {
-        set_error("mnk_bn_act_bwd_stats_sync: workspace too small");
-        return MNK_EWORKSPACE;
-    }
+    Map2D m;
+    int rc = partials_map(__func__, rows, 1, ldc, ws_floats, &m);
+    if (rc != MNK_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(K_BN_BWD, s, (double)N * H * W * C * 4 * (pool ? 1.25 : 2.0));
     BwdLoader L{y, dz, mean, invstd, scale, beta, ld_y, ld_dz, dz_off, H, W, C, pool, 0, relu ? 0.f : -1.f};
-    hipLaunchKernelGGL(colsum2_partial_kernel<BwdLoader>, dim3(m.col_tiles, m.row_blocks, 1), dim3(256), 0, s, L, rows, ldc / 4, ldc,
-                       m.tx, m.ty, m.rows_per_block, ws);
-    const int rc = launch_final_sync(p2p, ws, m.row_blocks, ldc, C, sums_local, sums_global, timeout_ms, s);
+    launch_partials(L, m, rows, 1, ldc, ws, s);
+    rc = launch_final_sync(__func__, p2p, ws, m.row_blocks, ldc, C, sums_local, sums_global, timeout_ms, s);
     if (rc != MNK_OK) return rc;
     MNK_LAUNCH_CHECK();
     return MNK_OK;
@@ -1371,20 +1352,33 @@ int mnk_bn_small_rows(void) { return g_small_rows; }
 int mnk_bn_small_fwd(const float* ws, int splits, int ldw, int phases, const float* bias, float* y, int ld_y, int N, int H, int W,
                      int C, const float* gamma, const float* beta, float* running_mean, float* running_var, float momentum,
                      float eps, float* mean, float* invstd, float* scale, float* z, int ld_z, int relu, int pool, void* stream) {
-    MNK_REQUIRE(y && gamma && beta && running_mean && running_var && mean && invstd && scale && z && N > 0 && H > 0 && W > 0);
-    MNK_REQUIRE(C > 0 && ld_y % 4 == 0 && ld_y == round_up(C, 4) && ld_z == ld_y && (long)N * H * W <= 4096 && (long)N * H * W > 1);
-    MNK_REQUIRE(!ws || (splits >= 1 && ldw == ld_y && (phases == 1 || (phases == 4 && H % 2 == 0 && W % 2 == 0))));
-    MNK_REQUIRE(!pool || (H % 2 == 0 && W % 2 == 0));
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(K_BN_APPLY, s, (double)N * H * W * C * 4 * 3.0);
-    SmallFwdArgs a{ws, splits, ldw, phases, bias, y, ld_y, N, H, W, C, gamma, beta, running_mean, running_var, momentum, eps,
-                   mean, invstd, scale, z, ld_z, relu, pool, small_txn(ld_y / 4)};
-    int threads;
-    small_shape(ld_y / 4, &threads, &a.tx_n);
-    MNK_REQUIRE(a.tx_n >= 1 && a.tx_n <= 64 && (a.tx_n & (a.tx_n - 1)) == 0);
-    hipLaunchKernelGGL(bn_small_fwd_kernel, dim3(ceil_div(ld_y / 4, a.tx_n)), dim3(threads), 0, s, a);
-    MNK_LAUNCH_CHECK();
-    return MNK_OK;
+    MNK_REQUIRE((long)N * H * W > 1);        // one rank: its rows are all the statistics have
+    return small_fwd(__func__, nullptr, 0, ws, splits, ldw, phases, bias, y, ld_y, N, H, W, C, gamma, beta, running_mean, running_var,
+                     momentum, eps, mean, invstd, scale, z, ld_z, relu, pool, (hipStream_t)stream);
+}
+
+int mnk_bn_small_fwd_sync(void* p2p, const float* ws, int splits, int ldw, int phases, const float* bias, float* y, int ld_y, int N,
+                          int H, int W, int C, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                          float momentum, float eps, float* mean, float* invstd, float* scale, float* z, int ld_z, int relu, int pool,
+                          int timeout_ms, void* stream) {
+    MNK_REQUIRE(p2p && timeout_ms > 0);      // (one row is enough here: the count is over the rows of all ranks)
+    return small_fwd(__func__, p2p, timeout_ms, ws, splits, ldw, phases, bias, y, ld_y, N, H, W, C, gamma, beta, running_mean, running_var,
+                     momentum, eps, mean, invstd, scale, z, ld_z, relu, pool, (hipStream_t)stream);
+}
+
+int mnk_bn_small_bwd(const float* y, int ld_y, const float* dz, int ld_dz, const float* mean, const float* invstd,
+                     const float* scale, const float* beta, double count, int N, int H, int W, int C, int relu, int pool,
+                     float* sums, float* dy, int ld_dy, void* stream) {
+    return small_bwd(__func__, nullptr, 0, y, ld_y, dz, ld_dz, mean, invstd, scale, beta, count, N, H, W, C, relu, pool, sums, dy, ld_dy,
+                     (hipStream_t)stream);
+}
+
+int mnk_bn_small_bwd_sync(void* p2p, const float* y, int ld_y, const float* dz, int ld_dz, const float* mean, const float* invstd,
+                          const float* scale, const float* beta, double count_all_ranks, int N, int H, int W, int C, int relu,
+                          int pool, float* sums_local, float* dy, int ld_dy, int timeout_ms, void* stream) {
+    MNK_REQUIRE(p2p && timeout_ms > 0);
+    return small_bwd(__func__, p2p, timeout_ms, y, ld_y, dz, ld_dz, mean, invstd, scale, beta, count_all_ranks, N, H, W, C, relu, pool, sums_local,
+                     dy, ld_dy, (hipStream_t)stream);
 }
 
 int mnk_bn_eval_split_fwd(const float* ws, int splits, int ldw, int phases, const float* bias, const float* mean, const float* scale,
@@ -1407,73 +1401,6 @@ int mnk_bn_eval_split_fwd(const float* ws, int splits, int ldw, int phases, cons
     const long orows = (long)N * (pool ? H / 2 : H) * (pool ? W / 2 : W);
     ProfScope prof(K_BN_APPLY, s, ((double)splits * N * H * W * ldw + (double)orows * ld_z) * 4);
     hipLaunchKernelGGL(bn_eval_split_fwd_kernel, dim3(ceil_div(nv, tx), ceil_div(orows, a.ty_n)), dim3(256), 0, s, a);
-    MNK_LAUNCH_CHECK();
-    return MNK_OK;
-}
-
-int mnk_bn_small_fwd_sync(void* p2p, const float* ws, int splits, int ldw, int phases, const float* bias, float* y, int ld_y, int N,
-                          int H, int W, int C, const float* gamma, const float* beta, float* running_mean, float* running_var,
-                          float momentum, float eps, float* mean, float* invstd, float* scale, float* z, int ld_z, int relu, int pool,
-                          int timeout_ms, void* stream) {
-    MNK_REQUIRE(p2p && y && gamma && beta && running_mean && running_var && mean && invstd && scale && z && N > 0 && H > 0 && W > 0);
-    MNK_REQUIRE(C > 0 && ld_y % 4 == 0 && ld_y == round_up(C, 4) && ld_z == ld_y && (long)N * H * W <= 4096 && timeout_ms > 0);
-    MNK_REQUIRE(!ws || (splits >= 1 && ldw == ld_y && (phases == 1 || (phases == 4 && H % 2 == 0 && W % 2 == 0))));
-    MNK_REQUIRE(!pool || (H % 2 == 0 && W % 2 == 0));
-    PeerTable peers;
-    int rank = 0, world = 0;
-    unsigned* state = nullptr;
-    if (!p2p_launch_info(p2p, &peers, &rank, &world, &state) || 2 * C > P2P_MAXF) {
-        set_error("mnk_bn_small_fwd_sync: the peer-to-peer exchange is not connected, or more than %d channels", P2P_MAXF / 2);
-        return MNK_ECOMM;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(K_BN_APPLY, s, (double)N * H * W * C * 4 * 3.0);
-    SmallFwdArgs a{ws, splits, ldw, phases, bias, y, ld_y, N, H, W, C, gamma, beta, running_mean, running_var, momentum, eps,
-                   mean, invstd, scale, z, ld_z, relu, pool, 1};
-    hipLaunchKernelGGL(bn_small_fwd_sync_kernel, dim3(ld_y / 4), dim3(256), 0, s, a, peers, rank, world, state,
-                       (unsigned long long)timeout_ms * 100000ull);
-    MNK_LAUNCH_CHECK();
-    return MNK_OK;
-}
-
-int mnk_bn_small_bwd(const float* y, int ld_y, const float* dz, int ld_dz, const float* mean, const float* invstd,
-                     const float* scale, const float* beta, double count, int N, int H, int W, int C, int relu, int pool,
-                     float* sums, float* dy, int ld_dy, void* stream) {
-    MNK_REQUIRE(y && dz && mean && invstd && scale && beta && sums && dy && N > 0 && H > 0 && W > 0 && C > 0 && count > 1);
-    MNK_REQUIRE(ld_y % 4 == 0 && ld_y >= round_up(C, 4) && ld_dy % 4 == 0 && ld_dy >= round_up(C, 4) && ld_dz >= C);
-    MNK_REQUIRE((long)N * H * W <= 4096 && (!pool || (H % 2 == 0 && W % 2 == 0)));
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(K_BN_BWD, s, (double)N * H * W * C * 4 * 5.0);
-    const int nv = round_up(C, 4) / 4;
-    int threads = 256, txn = small_txn(nv);
-    if (g_small_bwd_shape) small_shape(nv, &threads, &txn);
-    MNK_REQUIRE(txn >= 1 && txn <= 64 && (txn & (txn - 1)) == 0);
-    BwdLoader L{y, dz, mean, invstd, scale, beta, ld_y, ld_dz, 0, H, W, C, pool, 0, relu ? 0.f : -1.f};
-    hipLaunchKernelGGL(bn_small_bwd_kernel, dim3(ceil_div(nv, txn)), dim3(threads), 0, s, L, count, N * H * W, nv, txn, sums, dy, ld_dy);
-    MNK_LAUNCH_CHECK();
-    return MNK_OK;
-}
-
-int mnk_bn_small_bwd_sync(void* p2p, const float* y, int ld_y, const float* dz, int ld_dz, const float* mean, const float* invstd,
-                          const float* scale, const float* beta, double count_all_ranks, int N, int H, int W, int C, int relu,
-                          int pool, float* sums_local, float* dy, int ld_dy, int timeout_ms, void* stream) {
-    MNK_REQUIRE(p2p && y && dz && mean && invstd && scale && beta && sums_local && dy && N > 0 && H > 0 && W > 0 && C > 0);
-    MNK_REQUIRE(count_all_ranks > 1 && timeout_ms > 0);
-    MNK_REQUIRE(ld_y % 4 == 0 && ld_y >= round_up(C, 4) && ld_dy % 4 == 0 && ld_dy >= round_up(C, 4) && ld_dz >= C);
-    MNK_REQUIRE((long)N * H * W <= 4096 && (!pool || (H % 2 == 0 && W % 2 == 0)));
-    PeerTable peers;
-    int rank = 0, world = 0;
-    unsigned* state = nullptr;
-    if (!p2p_launch_info(p2p, &peers, &rank, &world, &state) || 2 * C > P2P_MAXF) {
-        set_error("mnk_bn_small_bwd_sync: the peer-to-peer exchange is not connected, or more than %d channels", P2P_MAXF / 2);
-        return MNK_ECOMM;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(K_BN_BWD, s, (double)N * H * W * C * 4 * 5.0);
-    const int nv = round_up(C, 4) / 4;
-    BwdLoader L{y, dz, mean, invstd, scale, beta, ld_y, ld_dz, 0, H, W, C, pool, 0, relu ? 0.f : -1.f};
-    hipLaunchKernelGGL(bn_small_bwd_sync_kernel, dim3(nv), dim3(256), 0, s, L, count_all_ranks, N * H * W, nv, sums_local, dy, ld_dy,
-                       peers, rank, world, state, (unsigned long long)timeout_ms * 100000ull);
     MNK_LAUNCH_CHECK();
     return MNK_OK;
 }

@@ -141,22 +141,26 @@ static inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
 
 }  // namespace mnk
 
-#define MNK_REQUIRE(cond)                                                        \
+// `who` names the entry point in the message: __func__, or what a shared implementation was told (MNK_REQUIRE_FOR)
+#define MNK_REQUIRE_AS(who, cond, text)                                          \
     do {                                                                         \
         if (!(cond)) {                                                           \
-            mnk::set_error("%s: invalid argument: %s", __func__, #cond);         \
+            mnk::set_error("%s: invalid argument: %s", who, text);               \
             return MNK_EINVAL;                                                   \
         }                                                                        \
     } while (0)
+#define MNK_REQUIRE(cond) MNK_REQUIRE_AS(__func__, cond, #cond)
+#define MNK_REQUIRE_FOR(who, cond) MNK_REQUIRE_AS(who, cond, #cond)
 
-#define MNK_LAUNCH_CHECK()                                                       \
+#define MNK_LAUNCH_CHECK_FOR(who)                                                \
     do {                                                                         \
         hipError_t e__ = hipGetLastError();                                      \
         if (e__ != hipSuccess) {                                                 \
-            mnk::set_error("%s: launch failed: %s", __func__, hipGetErrorString(e__)); \
+            mnk::set_error("%s: launch failed: %s", who, hipGetErrorString(e__)); \
             return MNK_ELAUNCH;                                                  \
         }                                                                        \
     } while (0)
+#define MNK_LAUNCH_CHECK() MNK_LAUNCH_CHECK_FOR(__func__)
 
 // ---- device helpers -------------------------------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {

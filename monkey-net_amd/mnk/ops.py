@@ -972,11 +972,11 @@ class BNActFn(_Fn):
         count = float(rows)
         pending = _SPLIT_PENDING.pop(y.data_ptr(), None)
         ctx.small = False
+        ho, wo = (h // 2, w // 2) if pool else (h, w)
+        z = torch.empty(n, ho, wo, ceil4(c), dtype=torch.float32, device=dev)     # every kernel zeroes the pad channels
         if small_bn(rows, training, c) and ld == ceil4(c) and h % (2 if pool else 1) == 0 and w % (2 if pool else 1) == 0:
             # the whole layer in one launch (csrc/batchnorm.hip: bn_small_fwd_kernel; several ranks: bn_small_fwd_sync_kernel,
             # the exchange of the sums inside the launch, statistics over the rows of ALL ranks)
-            ho, wo = (h // 2, w // 2) if pool else (h, w)
-            z = torch.empty(n, ho, wo, ceil4(c), dtype=torch.float32, device=dev)
             sp = pending if pending is not None else _NO_SPLIT
             if mdist.active():
                 count *= mdist.world_size()
@@ -995,8 +995,6 @@ class BNActFn(_Fn):
             # evaluation mode behind a split-K convolution (conv3x3(eval_bn=True), no_grad): reduction + affine + ReLU + pool in
             # one launch; y was never written and nothing is saved for a backward pass
             mean, invstd, scale = _bn_eval_coeffs(y, gamma, running_mean, running_var, eps, c)
-            ho, wo = (h // 2, w // 2) if pool else (h, w)
-            z = torch.empty(n, ho, wo, ceil4(c), dtype=torch.float32, device=dev)
             _call("mnk_bn_eval_split_fwd", y, _p(pending.ws), pending.splits, ld, pending.phases, _p(pending.bias), _p(mean), _p(scale), _p(beta), _p(z),
                   z.shape[-1], n, h, w, c, int(relu), int(pool))
             return z
@@ -1014,8 +1012,6 @@ class BNActFn(_Fn):
                     sums = mdist.all_reduce_sum(sums) if sums is pre_sums else mdist.all_reduce_sum_(sums)
                 count *= mdist.world_size()
                 # finalisation inside the apply pass (mnk_bn_act_fwd_sums): one launch less per norm layer on the SyncBN path
-                ho, wo = (h // 2, w // 2) if pool else (h, w)
-                z = torch.empty(n, ho, wo, ceil4(c), dtype=torch.float32, device=dev)
                 _call("mnk_bn_act_fwd_sums", y, _p(y), ld, _p(sums), count, _p(gamma), _p(beta), _p(running_mean),
                       _p(running_var), float(momentum), float(eps), 1, _p(mean), _p(invstd), _p(scale), _p(z), z.shape[-1], 0, n, h,
                       w, c, int(relu), int(pool))
@@ -1039,8 +1035,6 @@ class BNActFn(_Fn):
                           _p(ws), nws)
         else:
             mean, invstd, scale = _bn_eval_coeffs(y, gamma, running_mean, running_var, eps, c)
-        ho, wo = (h // 2, w // 2) if pool else (h, w)
-        z = torch.empty(n, ho, wo, ceil4(c), dtype=torch.float32, device=dev)     # the kernel zeroes the pad channels
         _call("mnk_bn_act_fwd", y, _p(y), ld, _p(mean), _p(scale), _p(beta), _p(z), z.shape[-1], 0, n, h, w, c, int(relu),
               int(pool))
         ctx.save_for_backward(y, mean, invstd, scale, beta)
@@ -1064,33 +1058,30 @@ class BNActFn(_Fn):
         if dskip is not None:
             dskip = dskip.contiguous()
             assert dskip.shape == y.shape, "the skip gradient of a residual block has the shape of the block's input"
-        if ctx.small and not mdist.active():
-            sums = torch.empty(2 * c, dtype=torch.float32, device=y.device)
+        # a small layer: statistics, (several ranks: their exchange inside the launch,) and the apply pass in ONE launch
+        # (mnk_bn_small_bwd / mnk_bn_small_bwd_sync) -- the general path spends three to four launches here
+        sync = None
+        small = ctx.small and not mdist.active()
+        if not small:
+            sync = _sync_handle(c) if training else None  # several ranks: the second stage carries the exchange of the sums
+            small = (sync is not None and _small_sync(rows) and ld == ceil4(c) and 2 * c <= mdist._P2P["max"]
+                     and (not pool or (h % 2 == 0 and w % 2 == 0)))
+        if small:
+            sums = torch.empty(2 * c, dtype=torch.float32, device=y.device)      # this rank's own: [dbeta | dgamma]
             dy = torch.empty(n, h, w, ld, dtype=torch.float32, device=y.device)
-            _call("mnk_bn_small_bwd", y, _p(y), ld, _p(dz), dz.shape[-1], _p(mean), _p(invstd), _p(scale), _p(beta), count, n, h,
-                  w, c, int(relu), int(pool), _p(sums), _p(dy), ld)
+            args = (_p(y), ld, _p(dz), dz.shape[-1], _p(mean), _p(invstd), _p(scale), _p(beta), count, n, h, w, c, int(relu),
+                    int(pool), _p(sums), _p(dy), ld)
+            if sync is None:
+                _call("mnk_bn_small_bwd", y, *args)
+            else:
+                _DZ_STATS.pop(dz.data_ptr(), None)
+                _call("mnk_bn_small_bwd_sync", y, sync, *args, mdist.P2P_TIMEOUT_MS)
             if dskip is not None:
                 dy = dy + dskip                # few-pixel layers: the one-launch kernel has no addend operand
                 _DY_SUMS[0] = None             # ... and the sum's column sums are not zero: the convolution in front makes them
             else:
                 _DY_SUMS[0] = (dy, None)
             return dy, sums[c:], sums[:c], None, None, None, None, None, None, None, None, None
-        sync = _sync_handle(c) if training else None      # several ranks: the second stage carries the exchange of the sums
-        if (sync is not None and _small_sync(rows) and ld == ceil4(c) and 2 * c <= mdist._P2P["max"]
-                and (not pool or (h % 2 == 0 and w % 2 == 0))):
-            # a small layer on one rank of several: statistics, their exchange and the apply pass in ONE launch, as the
-            # single-process path does it (mnk_bn_small_bwd) -- the general path spends three to four launches here
-            _DZ_STATS.pop(dz.data_ptr(), None)
-            local = torch.empty(2 * c, dtype=torch.float32, device=y.device)
-            dy = torch.empty(n, h, w, ld, dtype=torch.float32, device=y.device)
-            _call("mnk_bn_small_bwd_sync", y, sync, _p(y), ld, _p(dz), dz.shape[-1], _p(mean), _p(invstd), _p(scale), _p(beta),
-                  count, n, h, w, c, int(relu), int(pool), _p(local), _p(dy), ld, mdist.P2P_TIMEOUT_MS)
-            if dskip is not None:
-                dy = dy + dskip
-                _DY_SUMS[0] = None
-            else:
-                _DY_SUMS[0] = (dy, None)
-            return dy, local[c:], local[:c], None, None, None, None, None, None, None, None, None
         nws = _query("mnk_bn_workspace_floats", rows, ceil4(c))
         ws = SCRATCH.get("ws", nws, y)
         sums = torch.empty(2 * c, dtype=torch.float32, device=y.device)

@@ -530,6 +530,111 @@ def test_one_launch_small_layer_forms_with_the_exchange_inside(be, shape, pool):
         be.lib.call("mnk_p2p_destroy", hnd)
 
 
+# the thread maps of the one-launch forms: (bn_small_fwd_threads, bn_small_fwd_txn, bn_small_txn, bn_small_bwd_shape)
+_SMALL_MAP_KNOBS = (b"bn_small_fwd_threads", b"bn_small_fwd_txn", b"bn_small_txn", b"bn_small_bwd_shape")
+
+
+def _get_small_map(be):
+    import ctypes
+    out = []
+    for name in _SMALL_MAP_KNOBS:
+        v = ctypes.c_int(0)
+        be.lib.call("mnk_get_tuning", name, ctypes.byref(v))
+        out.append(v.value)
+    return tuple(out)
+
+
+def _set_small_map(be, values):
+    for name, v in zip(_SMALL_MAP_KNOBS, values):
+        be.lib.call("mnk_set_tuning", name, v)
+
+
+def _small_layer_case(shape, pool, seed):
+    """inputs of one small training-mode layer and its fp64 reference: F.batch_norm + relu (+ avg_pool2d), forward and backward"""
+    n, c, h, w = shape
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(n, c, h, w, generator=g) * 2 + 0.5
+    gamma, beta = torch.rand(c, generator=g) + 0.5, torch.randn(c, generator=g) * 0.3
+    rm0, rv0 = torch.randn(c, generator=g) * 0.1, torch.rand(c, generator=g) + 0.5
+    xd = x.double().requires_grad_(True)
+    gd, bd = gamma.double().requires_grad_(True), beta.double().requires_grad_(True)
+    rm, rv = rm0.double().clone(), rv0.double().clone()
+    z = F.relu(F.batch_norm(xd, rm, rv, gd, bd, True, 0.1, 1e-5))
+    if pool:
+        z = F.avg_pool2d(z, 2)
+    dz = torch.randn(z.shape, generator=g, dtype=torch.float64)
+    z.backward(dz)
+    return dict(x=x, gamma=gamma, beta=beta, rm0=rm0, rv0=rv0, dz=dz.float(), z=z.detach(), rm=rm, rv=rv, dx=xd.grad,
+                dgamma=gd.grad, dbeta=bd.grad)
+
+
+def _run_small_layer(be, case, shape, pool, hnd=None):
+    """mnk_bn_small_fwd + _bwd (hnd: the *_sync forms on that handle) -> the host copies of everything they write"""
+    n, c, h, w = shape
+    ld = ceil4(c)
+    ho, wo = (h // 2, w // 2) if pool else (h, w)
+    X, G, Bt = be.t(to_nhwc(case["x"])), be.t(case["gamma"]), be.t(case["beta"])
+    mean, invstd, scale = be.empty(c), be.empty(c), be.empty(c)
+    RM, RV, Z = be.t(case["rm0"].clone()), be.t(case["rv0"].clone()), be.empty(n, ho, wo, ld)
+    args = (None, 0, ld, 1, None, X, ld, n, h, w, c, G, Bt, RM, RV, 0.1, 1e-5, mean, invstd, scale, Z, ld, 1, pool)
+    if hnd is None:
+        be.call("mnk_bn_small_fwd", *args)
+    else:
+        be.call("mnk_bn_small_fwd_sync", hnd, *args, 2000)
+    DZ = be.t(to_nhwc(case["dz"]))
+    bs, DY = be.empty(2 * c), be.empty(n, h, w, ld)
+    args = (X, ld, DZ, ld, mean, invstd, scale, Bt, float(n * h * w), n, h, w, c, 1, pool, bs, DY, ld)
+    if hnd is None:
+        be.call("mnk_bn_small_bwd", *args)
+    else:
+        be.call("mnk_bn_small_bwd_sync", hnd, *args, 2000)
+    be.sync()
+    return dict(z=Z.cpu(), rm=RM.cpu(), rv=RV.cpu(), mean=mean.cpu(), invstd=invstd.cpu(), scale=scale.cpu(), sums=bs.cpu(),
+                dy=DY.cpu())
+
+
+@pytest.mark.parametrize("shape,pool", [((2, 10, 4, 4), 0), ((4, 37, 4, 6), 1), ((2, 130, 2, 2), 0)])
+def test_one_launch_small_layer_forms_equal_their_sync_forms_bit_for_bit_on_the_same_thread_map(be, shape, pool):
+    """mnk_bn_small_fwd / _bwd on the *_sync kernels' thread map (256 threads, one channel quad per block; the backward default
+    already is that map) against mnk_bn_small_fwd_sync / _bwd_sync on a one-rank handle: one body, so every output is equal bit
+    for bit -- z, both running statistics, mean, inv-std, scale; dy and the 2c sums.  37 channels: a guarded tail quad; the 2x2
+    maps: 8 rows for 256 threads."""
+    case = _small_layer_case(shape, pool, 4)
+    hnd = _one_rank_handle(be)
+    before = _get_small_map(be)
+    try:
+        _set_small_map(be, (256, 1) + before[2:])
+        plain = _run_small_layer(be, case, shape, pool)
+        sync = _run_small_layer(be, case, shape, pool, hnd)
+    finally:
+        _set_small_map(be, before)
+        be.lib.call("mnk_p2p_destroy", hnd)
+    for key in ("z", "rm", "rv", "mean", "invstd", "scale", "dy", "sums"):
+        assert torch.equal(plain[key], sync[key]), key
+
+
+@pytest.mark.parametrize("fwd_threads,fwd_txn,small_txn,bwd_shape", [(256, 1, 1, 0), (512, 4, 4, 0), (1024, 8, 0, 1), (256, -1, 2, 1)])
+@pytest.mark.parametrize("shape,pool", [((4, 37, 4, 6), 1), ((2, 130, 2, 2), 0), ((3, 5, 2, 2), 0)])
+def test_every_thread_map_of_the_one_launch_small_layer_forms(be, shape, pool, fwd_threads, fwd_txn, small_txn, bwd_shape):
+    """mnk_bn_small_fwd / _bwd on the non-default thread maps of the shared bodies against F.batch_norm(training) + relu +
+    avg_pool2d in fp64, with the bounds of the default map (test_bn_small_layer_one_launch_forms).  Eight quads per block leave
+    blocks with lanes beyond the last quad on 33 and 10 quads; (3, 5, 2, 2) is 12 rows on 2 quads."""
+    n, c, h, w = shape
+    case = _small_layer_case(shape, pool, 3)
+    before = _get_small_map(be)
+    try:
+        _set_small_map(be, (fwd_threads, fwd_txn, small_txn, bwd_shape))
+        out = _run_small_layer(be, case, shape, pool)
+    finally:
+        _set_small_map(be, before)
+    assert maxerr(from_nhwc(out["z"], c), case["z"]) < 2e-5
+    assert torch.all(out["z"][..., c:] == 0)
+    assert maxerr(out["rm"], case["rm"]) < 1e-5 and maxerr(out["rv"], case["rv"]) < 1e-4
+    assert relerr(out["sums"][:c], case["dbeta"]) < 1e-4 and relerr(out["sums"][c:], case["dgamma"]) < 1e-4
+    assert relerr(from_nhwc(out["dy"], c), case["dx"]) < 1e-4
+    assert torch.all(out["dy"][..., c:] == 0)
+
+
 @pytest.mark.parametrize("splits", [1, 2, 3, 4, 5, 8, 13, 33])
 @pytest.mark.parametrize("phases,pool,relu,c", [(1, 0, 1, 22), (1, 1, 1, 45), (4, 0, 1, 3), (4, 1, 0, 66), (1, 1, 0, 7)])
 def test_eval_norm_layer_on_split_partials(be, splits, phases, pool, relu, c):
