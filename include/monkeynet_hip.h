@@ -56,6 +56,10 @@ int mnk_prof_query_executed(int kernel_id, double* executed_work);
 int mnk_ncdhw_to_nhwc(const float* src, float* dst, int B, int C, int D, int H, int W, int step, int ld_dst,
                       void* stream);
 int mnk_nhwc_to_ncdhw(const float* src, int ld_src, float* dst, int B, int C, int D, int H, int W, void* stream);
+/* adjoint of mnk_ncdhw_to_nhwc with step >= 1: src [B*D][H/step][W/step][ld_src] -> dst (B,C,D,H,W), the picked pixels
+ * [..., ::step, ::step] get the act's values, every other element 0 (all of dst is written) */
+int mnk_nhwc_to_ncdhw_strided(const float* src, int ld_src, float* dst, int B, int C, int D, int H, int W, int step,
+                              void* stream);
 /* dst[r, dst_off + c] = src[r, src_off + c], c < C (torch.cat / slicing: modules/util.py:185, generator.py:73) */
 int mnk_copy_channels(const float* src, int ld_src, int src_off, float* dst, int ld_dst, int dst_off, int C,
                       long rows, int accumulate, void* stream);
@@ -564,14 +568,20 @@ int mnk_movement_embedding_fwd(const float* img, int ld_img, int Cimg, const flo
                                float* out, int ld_out, void* stream);
 /* gradients w.r.t. the key-points, one row per frame: dmean_d/dvar_d/dmean_s/dvar_s [Nb*d][K][2|4] (the caller sums
  * the source gradients over the d frames of a batch entry).  Overwritten.  dvar_* may both be NULL (constant
- * variance).  The gradient w.r.t. the source image is not produced: no caller of the reference consumes it
- * (SURVEY.md section 8b "Gradients"). */
+ * variance).  The gradient w.r.t. the source image is mnk_movement_embedding_img_bwd's. */
 int mnk_movement_embedding_bwd(const float* img, int ld_img, int Cimg, const float* mean_d, const float* var_d,
                                const float* mean_s, const float* var_s, float const_var, int Nb, int d, int h, int w,
                                int K, int add_bg, int use_heatmap, int use_difference, int use_deformed,
                                int heatmap_diff, float norm_const, const float* norm_d, const float* norm_s,
                                const float* dout, int ld_out, float* dmean_d, float* dvar_d, float* dmean_s,
                                float* dvar_s, void* stream);
+/* use_deformed_source_image (movement_embedding.py:76-87): the gradient w.r.t. the source image, dimg [Nb][h][w][ld_img] --
+ * image b collects the d frames of its video and all K + add_bg slots of each.  No caller of the reference consumes it
+ * (SURVEY.md section 8b "Gradients"), so it is a launch of its own that runs only when the image asks for a gradient.  A gather
+ * per image texel in a fixed order (frames, slots, pixels): deterministic.  WRITTEN, pad channels 0. */
+int mnk_movement_embedding_img_bwd(int ld_img, int Cimg, const float* mean_d, const float* mean_s, int Nb, int d, int h, int w,
+                                   int K, int add_bg, int use_heatmap, int use_difference, const float* dout, int ld_out,
+                                   float* dimg, void* stream);
 
 /* ---- dense-motion head (modules/dense_motion_module.py:52-76) --------------------------------------------
  * pred [N][h][w][ld]: channels [0,K+1) mask logits (use_mask), last 2 correction (use_correction);
@@ -606,6 +616,18 @@ size_t mnk_deform_bwd_workspace_floats(int C, int h, int w, int N);
 int mnk_deform_bwd(const float* inp, int ld_in, int C, int h, int w, const float* field, int hf, int wf, int mode,
                    const float* dout, int ld_out, int out_off, float* dinp, float* dfield, int N, float* ws, size_t ws_floats,
                    void* stream);
+/* Several driving frames per source image (generator.py:51-58,60-78: deform_input repeats the source along the depth axis and
+ * warps every copy by its own frame of the field; here the source is read in place instead of being repeated).  field, out and
+ * dout have N = videos * frames rows in the order v*frames + f; inp and dinp hold N / frames images, and row n reads image
+ * n / frames.  N % frames != 0 is MNK_EINVAL and nothing is launched.  frames = 1 is mnk_deform_fwd / mnk_deform_bwd themselves
+ * (the same code).  Backward: dinp of a texel sums the frames of its video in order, the pixels of each frame in pixel order -- a
+ * fixed order, no atomics; it is WRITTEN, pad channels 0.  frames * h * w must fit an int.  The workspace is the plain entry's:
+ * mnk_deform_bwd_workspace_floats(C, h, w, N) with N the number of FIELD rows. */
+int mnk_deform_shared_fwd(const float* inp, int ld_in, int C, int h, int w, const float* field, int hf, int wf, int mode,
+                          float* out, int ld_out, int out_off, int N, int frames, void* stream);
+int mnk_deform_shared_bwd(const float* inp, int ld_in, int C, int h, int w, const float* field, int hf, int wf, int mode,
+                          const float* dout, int ld_out, int out_off, float* dinp, float* dfield, int N, int frames, float* ws,
+                          size_t ws_floats, void* stream);
 /* All warps of one generator pass in ONE launch each way (generator.py:60-78: every decoder level's appearance skip is
  * warped by the same field, resized per level (mode 0: nearest pick, mode 1: bilinear -- 'trilinear' with unchanged depth, the
  * vox configs), and the key-point embedding is resized the same way into the channels behind it):
@@ -627,6 +649,15 @@ int mnk_warp_levels_fwd(const MnkWarpLevel* levels, int nlevels, const float* fi
 size_t mnk_warp_levels_bwd_workspace_floats(const MnkWarpLevel* levels, int nlevels, int N);
 int mnk_warp_levels_bwd(const MnkWarpLevel* levels, int nlevels, const float* field, int hf, int wf, int mode, float* dfield,
                         float* demb, int ld_emb, int He, int We, int N, float* ws, size_t ws_floats, void* stream);
+/* The same with several driving frames per source image (generator.py:51-58,60-78): field, emb, out_l, dout_l, dfield and demb
+ * have N = videos * frames rows in the order v*frames + f; inp_l and dinp_l hold N / frames images, and row n reads image
+ * n / frames (see mnk_deform_shared_fwd).  N % frames != 0 is MNK_EINVAL and nothing is launched; frames = 1 is the pair above.
+ * The workspace is mnk_warp_levels_bwd_workspace_floats(levels, nlevels, N) with N the number of FIELD rows. */
+int mnk_warp_levels_shared_fwd(const MnkWarpLevel* levels, int nlevels, const float* field, int hf, int wf, int mode,
+                               const float* emb, int ld_emb, int He, int We, int N, int frames, void* stream);
+int mnk_warp_levels_shared_bwd(const MnkWarpLevel* levels, int nlevels, const float* field, int hf, int wf, int mode,
+                               float* dfield, float* demb, int ld_emb, int He, int We, int N, int frames, float* ws,
+                               size_t ws_floats, void* stream);
 
 /* ---- feature-matching L1 on the discriminator's activations (modules/losses.py:8-12 reconstruction_loss over
  * discriminator maps; train.py:47-51) ---------------------------------------------------------------------------

@@ -642,6 +642,80 @@ __global__ void __launch_bounds__(256) movement_embedding_bwd_kernel(EmbedArgs a
     }
 }
 
+// pixels j of a size-n axis whose sample of the image, translated by dd (movement_embedding.py:80-85), has its left / upper
+// texel at t - 1 or t: ix(j) = ((grid_coord(j) + dd + 1) / 2) * (n - 1) is j + dd * (n - 1) / 2 up to rounding and does not
+// decrease with j, so they lie around t - dd * (n - 1) / 2; the caller tests every candidate with the forward's own arithmetic
+__device__ __forceinline__ bool translated_window(int t, float dd, int n, int& lo, int& hi) {
+    const float c = (float)t - dd * ((float)(n - 1) * 0.5f);
+    if (!(c > -2.f && c < (float)n + 1.f)) return false;        // (also: dd not finite)
+    const int pc = (int)floorf(c);
+    lo = pc - 2 > 0 ? pc - 2 : 0;
+    hi = pc + 3 < n - 1 ? pc + 3 : n - 1;
+    return lo <= hi;
+}
+
+// weight of texel t in the sample of pixel j: the forward's own factors (Bilin::setup), 0 when the sample does not touch it
+__device__ __forceinline__ bool translated_weight(int j, int t, float dd, int n, float& wgt) {
+    const float i = ((grid_coord(j, n) + dd + 1.f) / 2.f) * (float)(n - 1);
+    const float f = floorf(i);
+    if (f == (float)t) {
+        wgt = (f + 1.f) - i;
+        return true;
+    }
+    if (f + 1.f == (float)t) {
+        wgt = i - f;
+        return true;
+    }
+    return false;
+}
+
+// gradient of the source image under use_deformed_source_image (movement_embedding.py:76-87: the image is sampled once per
+// frame and key-point slot, translated by kp_source - kp_driving; the background slot is not translated).  grid_sample's
+// adjoint as a GATHER, like the warps of motion.hip: a thread owns one (image, texel, channel) and adds, over the frames of its
+// video in order, the slots in order, the pixels in pixel order, weight * dout of the pixels whose sample touches the texel --
+// a fixed order, no atomics.  d img is WRITTEN, pad channels 0.
+__global__ void __launch_bounds__(256) movement_embedding_img_bwd_kernel(EmbedArgs a, const float* __restrict__ dout,
+                                                                         int ld_out, float* __restrict__ dimg) {
+    const long P = (long)a.h * a.w;
+    const long total = (long)a.Nb * P * a.ld_img;
+    const int off_img = a.use_heatmap + 2 * a.use_difference;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int c = (int)(i % a.ld_img);
+        const long bp = i / a.ld_img;
+        if (c >= a.Cimg) {
+            dimg[i] = 0.f;
+            continue;
+        }
+        const int p = (int)(bp % P);
+        const int b = (int)(bp / P);
+        const int tx = p % a.w, ty = p / a.w;
+        float acc = 0.f;
+        for (int f = b * a.d; f < (b + 1) * a.d; ++f) {
+            const float* gf = dout + (long)f * P * ld_out + off_img + c;
+            for (int s = 0; s < a.slots; ++s) {
+                const int k = s - a.add_bg;
+                float ddx = 0.f, ddy = 0.f;
+                if (k >= 0) {
+                    ddx = a.mean_s[((long)b * a.K + k) * 2] - a.mean_d[((long)f * a.K + k) * 2];
+                    ddy = a.mean_s[((long)b * a.K + k) * 2 + 1] - a.mean_d[((long)f * a.K + k) * 2 + 1];
+                }
+                int x_lo, x_hi, y_lo, y_hi;
+                if (!translated_window(tx, ddx, a.w, x_lo, x_hi) || !translated_window(ty, ddy, a.h, y_lo, y_hi)) continue;
+                for (int py = y_lo; py <= y_hi; ++py) {
+                    float wy;
+                    if (!translated_weight(py, ty, ddy, a.h, wy)) continue;
+                    for (int px = x_lo; px <= x_hi; ++px) {
+                        float wx;
+                        if (!translated_weight(px, tx, ddx, a.w, wx)) continue;
+                        acc += gf[((long)py * a.w + px) * ld_out + s * a.per] * (wx * wy);
+                    }
+                }
+            }
+        }
+        dimg[i] = acc;
+    }
+}
+
 static inline int grid_for(long total, int cap = 4096) {
     long b = (total + 255) / 256;
     if (b < 1) b = 1;
@@ -1070,6 +1144,23 @@ int mnk_movement_embedding_bwd(const float* img, int ld_img, int Cimg, const flo
     ProfScope prof(K_EMBED, s, (double)Nb * d * h * w * K * per * 4);
     hipLaunchKernelGGL(movement_embedding_bwd_kernel, dim3(Nb * d * K), dim3(256), 0, s, a, dout, ld_out, dmean_d, dvar_d,
                        dmean_s, dvar_s);
+    MNK_LAUNCH_CHECK();
+    return MNK_OK;
+}
+
+int mnk_movement_embedding_img_bwd(int ld_img, int Cimg, const float* mean_d, const float* mean_s, int Nb, int d, int h, int w,
+                                   int K, int add_bg, int use_heatmap, int use_difference, const float* dout, int ld_out,
+                                   float* dimg, void* stream) {
+    MNK_REQUIRE(mean_d && mean_s && dout && dimg && Nb > 0 && d > 0 && h > 1 && w > 1 && K > 0);
+    MNK_REQUIRE(Cimg > 0 && ld_img >= Cimg && (long)Nb * d <= 0x7fffffffl);
+    EmbedArgs a;
+    int per = fill_embed_args(a, nullptr, ld_img, Cimg, mean_d, nullptr, mean_s, nullptr, 0.f, Nb, d, h, w, K, add_bg, use_heatmap,
+                              use_difference, 1, 0, 0.f, nullptr, nullptr);
+    MNK_REQUIRE(per > 0 && ld_out >= a.slots * per);
+    hipStream_t s = (hipStream_t)stream;
+    const long total = (long)Nb * h * w * ld_img;
+    ProfScope prof(K_EMBED, s, (double)Nb * d * h * w * a.slots * Cimg * 4);
+    hipLaunchKernelGGL(movement_embedding_img_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, s, a, dout, ld_out, dimg);
     MNK_LAUNCH_CHECK();
     return MNK_OK;
 }

@@ -46,6 +46,29 @@ __global__ void __launch_bounds__(256) nhwc_to_ncdhw_kernel(const float* __restr
     }
 }
 
+// adjoint of ncdhw_to_nhwc_kernel with step > 1: element (h, w) of the full-size gradient is the act's row (h / step, w / step)
+// where both are multiples of step (and inside the H / step x W / step map), 0 elsewhere; every element is written
+__global__ void __launch_bounds__(256) nhwc_to_ncdhw_strided_kernel(const float* __restrict__ src, int ld,
+                                                                    float* __restrict__ dst, int B, int C, int D, int H,
+                                                                    int W, int step) {
+    const int Ho = H / step, Wo = W / step;
+    const long total = (long)B * C * D * H * W;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int w = (int)(i % W);
+        long t = i / W;
+        const int h = (int)(t % H);
+        t /= H;
+        const int d = (int)(t % D);
+        t /= D;
+        const int c = (int)(t % C);
+        const int b = (int)(t / C);
+        float v = 0.f;
+        if (h % step == 0 && w % step == 0 && h / step < Ho && w / step < Wo)
+            v = src[((((long)b * D + d) * Ho + h / step) * Wo + w / step) * ld + c];
+        dst[i] = v;
+    }
+}
+
 __global__ void __launch_bounds__(256) copy_channels_kernel(const float* __restrict__ src, int ld_src, int src_off,
                                                             float* __restrict__ dst, int ld_dst, int dst_off, int C,
                                                             long rows, int accumulate) {
@@ -295,6 +318,19 @@ int mnk_nhwc_to_ncdhw(const float* src, int ld_src, float* dst, int B, int C, in
     long total = (long)B * D * H * W;
     ProfScope prof(K_LAYOUT, s, (double)total * (C + ld_src) * 4);
     hipLaunchKernelGGL(nhwc_to_ncdhw_kernel, dim3(grid_for(total)), dim3(256), 0, s, src, ld_src, dst, B, C, D, H, W);
+    MNK_LAUNCH_CHECK();
+    return MNK_OK;
+}
+
+int mnk_nhwc_to_ncdhw_strided(const float* src, int ld_src, float* dst, int B, int C, int D, int H, int W, int step,
+                              void* stream) {
+    MNK_REQUIRE(src && dst && B > 0 && C > 0 && D > 0 && H > 0 && W > 0 && ld_src >= C && step >= 1 && H / step > 0 &&
+                W / step > 0);
+    hipStream_t s = (hipStream_t)stream;
+    const long total = (long)B * C * D * H * W;
+    ProfScope prof(K_LAYOUT, s, (double)total * 4 + (double)B * D * (H / step) * (W / step) * C * 4);
+    hipLaunchKernelGGL(nhwc_to_ncdhw_strided_kernel, dim3(grid_for(total)), dim3(256), 0, s, src, ld_src, dst, B, C, D, H, W,
+                       step);
     MNK_LAUNCH_CHECK();
     return MNK_OK;
 }

@@ -819,8 +819,9 @@ struct Bilin {
 // sub-range of the blocks of a multi-level launch (warp_levels_*_kernel)
 __device__ __forceinline__ void deform_fwd_body(const float* __restrict__ inp, int ld_in, int C, int h, int w,
                                                 const float* __restrict__ field, int hf, int wf, int mode,
-                                                float* __restrict__ out, int ld_out, int out_off, int N, int vb, int vgrid,
-                                                bool zero_tail = false) {
+                                                float* __restrict__ out, int ld_out, int out_off, int N, int frames, int vb,
+                                                int vgrid, bool zero_tail = false) {
+    // frames: field / output rows per source image (rows v*frames + f of video v read image v; 1: an image per row)
     // zero_tail: nothing follows the C channels in the row (no embedding): the last quad's pad channels are written 0
     const int nq = (C + 3) / 4;
     const long P = (long)h * w;
@@ -836,7 +837,7 @@ __device__ __forceinline__ void deform_fwd_body(const float* __restrict__ inp, i
         fa.eval(field, n, hf, wf, py, px, h, w, mode);
         Bilin bl;
         bl.setup(fa.x, fa.y, w, h);
-        const float* ib = inp + n * P * ld_in + q * 4;
+        const float* ib = inp + (frames == 1 ? n : n / frames) * P * ld_in + q * 4;
         float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
         if (bl.y0ok && bl.x0ok) {
             const float4 v = *reinterpret_cast<const float4*>(ib + ((long)bl.y0 * w + bl.x0) * ld_in);
@@ -872,8 +873,9 @@ __device__ __forceinline__ void deform_fwd_body(const float* __restrict__ inp, i
 
 __global__ void __launch_bounds__(256) deform_fwd_kernel(const float* __restrict__ inp, int ld_in, int C, int h, int w,
                                                          const float* __restrict__ field, int hf, int wf, int mode,
-                                                         float* __restrict__ out, int ld_out, int out_off, int N) {
-    deform_fwd_body(inp, ld_in, C, h, w, field, hf, wf, mode, out, ld_out, out_off, N, blockIdx.x, gridDim.x);
+                                                         float* __restrict__ out, int ld_out, int out_off, int N,
+                                                         int frames) {
+    deform_fwd_body(inp, ld_in, C, h, w, field, hf, wf, mode, out, ld_out, out_off, N, frames, blockIdx.x, gridDim.x);
 }
 
 // ---- backward of the warps: deterministic, no floating-point atomics ---------------------------------------------------
@@ -885,7 +887,7 @@ __global__ void __launch_bounds__(256) deform_fwd_kernel(const float* __restrict
 //     pixel's share of the field gradient -- sum over channels of dout * d(sample)/d(ix, iy), CL lanes per pixel, channel
 //     slices over blockIdx.y, finished with wavefront shuffles -- goes to gpart[slice][pixel][2].  Nothing is added to
 //     anything shared.
-//   pass B, per SOURCE TEXEL (warp_bwd_gather_body): a block owns a T x T tile of one frame's texels.  It scans the frame's
+//   pass B, per SOURCE TEXEL (warp_bwd_gather_body): a block owns a T x T tile of one image's texels.  It scans the image's
 //     sampling points in pixel order, WG_BATCH at a time, and compacts those whose 2 x 2 footprint touches the tile into an
 //     LDS list IN PIXEL ORDER (wavefront ballots + popcounts of the lower lanes: no atomics either); then every
 //     (texel, channel quad) thread walks the list and accumulates weight * dout[pixel] of the entries that touch its texel.
@@ -906,8 +908,8 @@ __device__ __forceinline__ int lane_prefix_count(unsigned long long m) {     // 
 __device__ __forceinline__ void warp_bwd_pixel_body(const float* __restrict__ inp, int ld_in, int C, int h, int w,
                                                     const float* __restrict__ field, int hf, int wf, int mode,
                                                     const float* __restrict__ dout, int ld_out, int out_off,
-                                                    float* __restrict__ samp, float* __restrict__ gpart, int N, int CL,
-                                                    int cslice, int vbx, int vgx, int vby) {
+                                                    float* __restrict__ samp, float* __restrict__ gpart, int N, int frames,
+                                                    int CL, int cslice, int vbx, int vgx, int vby) {
     const long P = (long)h * w;
     const long npix = (long)N * P;
     const int ppb = 256 / CL;   // pixels per block iteration
@@ -929,7 +931,7 @@ __device__ __forceinline__ void warp_bwd_pixel_body(const float* __restrict__ in
                 samp[np * 2 + 1] = bl.iy;
             }
             if (gpart) {
-                const float* ib = inp + n * P * ld_in;
+                const float* ib = inp + (frames == 1 ? n : n / frames) * P * ld_in;
                 const long o_nw = ((long)bl.y0 * w + bl.x0) * ld_in, o_ne = o_nw + ld_in;
                 const long o_sw = o_nw + (long)w * ld_in, o_se = o_sw + ld_in;
                 const bool k_nw = bl.y0ok && bl.x0ok, k_ne = bl.y0ok && bl.x1ok, k_sw = bl.y1ok && bl.x0ok, k_se = bl.y1ok && bl.x1ok;
@@ -967,11 +969,13 @@ __device__ __forceinline__ float4 load4_channels(const float* __restrict__ row, 
     return v;
 }
 
-// vb = ((frame * tiles + tile) * qslices + quad slice); 256 threads = T*T texels x QL = 256 / (T*T) lanes per texel; a thread
-// owns channel quads qbase + a * QL + ql, a < nacc <= WG_MAXACC
+// vb = ((source image * tiles + tile) * qslices + quad slice); 256 threads = T*T texels x QL = 256 / (T*T) lanes per texel; a
+// thread owns channel quads qbase + a * QL + ql, a < nacc <= WG_MAXACC.  frames: output rows per source image -- rows
+// n*frames .. n*frames + frames - 1 are adjacent, so the block scans P = frames*h*w sampling points (the entry checks that it
+// fits an int) and a texel's sum runs frame-major, then in pixel order
 __device__ __forceinline__ void warp_bwd_gather_body(const float* __restrict__ dout, int ld_out, int out_off, int C, int h,
                                                      int w, const float* __restrict__ samp, float* __restrict__ dinp,
-                                                     int ld_in, int T, int nacc, int qslices, int vb) {
+                                                     int ld_in, int T, int nacc, int qslices, int frames, int vb) {
     __shared__ float s_ix[WG_BATCH], s_iy[WG_BATCH];
     __shared__ int s_p[WG_BATCH];
     __shared__ int s_cnt[2 * 16];
@@ -986,7 +990,7 @@ __device__ __forceinline__ void warp_bwd_gather_body(const float* __restrict__ d
     const bool active = tx < w && ty < h;
     const int nq = ld_in >> 2;
     const int qbase = slice * nacc * QL;
-    const int P = h * w;
+    const int P = frames * h * w;
     const float* sb = samp + (long)n * P * 2;
     const float* db = dout + (long)n * P * ld_out + out_off;
     const bool vec = ((out_off & 3) == 0) && ((ld_out & 3) == 0);
@@ -1138,6 +1142,7 @@ struct WarpSeg {          // one level's share of the launch
 struct WarpSegs {
     WarpSeg lv[MAX_WARP_LEVELS];
     int n, N, hf, wf, mode, ld_emb, He, We;
+    int frames;               // field / output rows per source image: level l's inp and dinp hold N / frames images
     const float* field;
     const float* emb;
     float* dfield;
@@ -1151,8 +1156,8 @@ __global__ void __launch_bounds__(256) warp_levels_fwd_kernel(WarpSegs a) {
     for (int l = 0; l < a.n; ++l) {
         const WarpSeg& L = a.lv[l];
         if (b >= L.warp_begin && b < L.warp_begin + L.warp_blocks) {
-            deform_fwd_body(L.inp, L.ld_in, L.C, L.h, L.w, a.field, a.hf, a.wf, a.mode, L.out, L.ld_out, 0, a.N, b - L.warp_begin,
-                            L.warp_blocks, L.ke == 0);
+            deform_fwd_body(L.inp, L.ld_in, L.C, L.h, L.w, a.field, a.hf, a.wf, a.mode, L.out, L.ld_out, 0, a.N, a.frames,
+                            b - L.warp_begin, L.warp_blocks, L.ke == 0);
             return;
         }
         if (b >= L.emb_begin && b < L.emb_begin + L.emb_blocks) {
@@ -1196,7 +1201,7 @@ __global__ void __launch_bounds__(256) warp_levels_bwd_pixel_kernel(WarpSegs a) 
         if (b >= L.warp_begin && b < L.warp_begin + L.warp_blocks) {
             const int vb = b - L.warp_begin;
             warp_bwd_pixel_body(L.inp, L.ld_in, L.C, L.h, L.w, a.field, a.hf, a.wf, a.mode, L.dout, L.ld_out, L.out_off, L.samp,
-                                a.dfield ? L.gpart : nullptr, a.N, L.CL, L.cslice, vb % L.gx, L.gx, vb / L.gx);
+                                a.dfield ? L.gpart : nullptr, a.N, a.frames, L.CL, L.cslice, vb % L.gx, L.gx, vb / L.gx);
             return;
         }
     }
@@ -1443,7 +1448,7 @@ __global__ void __launch_bounds__(256) warp_levels_bwd_gather_kernel(WarpSegs a)
         const WarpSeg& L = a.lv[l];
         if (b >= L.gat_begin && b < L.gat_begin + L.gat_blocks) {
             warp_bwd_gather_body(L.dout, L.ld_out, L.out_off, L.C, L.h, L.w, L.samp, L.dinp, L.ld_in, L.T, L.nacc, L.qslices,
-                                 b - L.gat_begin);
+                                 a.frames, b - L.gat_begin);
             return;
         }
     }
@@ -1667,17 +1672,29 @@ int mnk_motion_field_kp_bwd(const float* pred, int ld, const float* mean_s, cons
     return MNK_OK;
 }
 
-int mnk_deform_fwd(const float* inp, int ld_in, int C, int h, int w, const float* field, int hf, int wf, int mode,
-                   float* out, int ld_out, int out_off, int N, void* stream) {
+// the frames of one video share its source image: N rows of field and output, N / frames images (frames = 1: the plain entries)
+static int warp_frames_check(int N, int frames) {
+    MNK_REQUIRE(frames > 0 && N % frames == 0);
+    return MNK_OK;
+}
+
+int mnk_deform_shared_fwd(const float* inp, int ld_in, int C, int h, int w, const float* field, int hf, int wf, int mode,
+                          float* out, int ld_out, int out_off, int N, int frames, void* stream) {
     MNK_REQUIRE(inp && field && out && N > 0 && C > 0 && h > 0 && w > 0 && hf > 0 && wf > 0 && (mode == 0 || mode == 1));
     MNK_REQUIRE(ld_in % 4 == 0 && ld_in >= round_up(C, 4) && out_off >= 0 && out_off + C <= ld_out);
+    if (int rc = warp_frames_check(N, frames)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const long total = (long)N * h * w * ((C + 3) / 4);
     ProfScope prof(K_DEFORM, s, (double)N * h * w * C * 8);
     hipLaunchKernelGGL(deform_fwd_kernel, dim3(grid_for(total)), dim3(256), 0, s, inp, ld_in, C, h, w, field, hf, wf, mode,
-                       out, ld_out, out_off, N);
+                       out, ld_out, out_off, N, frames);
     MNK_LAUNCH_CHECK();
     return MNK_OK;
+}
+
+int mnk_deform_fwd(const float* inp, int ld_in, int C, int h, int w, const float* field, int hf, int wf, int mode,
+                   float* out, int ld_out, int out_off, int N, void* stream) {
+    return mnk_deform_shared_fwd(inp, ld_in, C, h, w, field, hf, wf, mode, out, ld_out, out_off, N, 1, stream);
 }
 
 static void warp_bwd_plan(int C, long npix, int& CL, int& cslice, int& gx, int& slices) {
@@ -1732,6 +1749,9 @@ static size_t warp_level_ws_floats(int C, int h, int w, int N) {
 // fills the plans and workspace pointers of a.lv[0 .. a.n) (inp, dout, dinp, ld_in, C, h, w, ld_out, out_off, ke, emb_off set by
 // the caller) and launches the two passes
 static int warp_bwd_launch(WarpSegs& a, float* ws, size_t ws_floats, double bytes, hipStream_t s) {
+    if (int rc = warp_frames_check(a.N, a.frames)) return rc;
+    // (the gather pass numbers the frames * h * w sampling points of a source image with an int)
+    for (int l = 0; l < a.n; ++l) MNK_REQUIRE((long)a.frames * a.lv[l].h * a.lv[l].w <= 0x7fffffffl);
     size_t need = 0;
     for (int l = 0; l < a.n; ++l) need += warp_level_ws_floats(a.lv[l].C, a.lv[l].h, a.lv[l].w, a.N);
     if (!ws || ws_floats < need) {
@@ -1766,7 +1786,7 @@ static int warp_bwd_launch(WarpSegs& a, float* ws, size_t ws_floats, double byte
         if (L.dinp) {
             int tiles;
             warp_gather_plan(L.ld_in, L.h, L.w, L.T, L.nacc, L.qslices, tiles);
-            const long nb = (long)a.N * tiles * L.qslices;
+            const long nb = (long)(a.N / a.frames) * tiles * L.qslices;
             MNK_REQUIRE(nb < (1l << 30));
             L.gat_blocks = (int)nb;
         }
@@ -1786,18 +1806,25 @@ size_t mnk_deform_bwd_workspace_floats(int C, int h, int w, int N) {
     return warp_level_ws_floats(C, h, w, N);
 }
 
-int mnk_deform_bwd(const float* inp, int ld_in, int C, int h, int w, const float* field, int hf, int wf, int mode,
-                   const float* dout, int ld_out, int out_off, float* dinp, float* dfield, int N, float* ws, size_t ws_floats,
-                   void* stream) {
+int mnk_deform_shared_bwd(const float* inp, int ld_in, int C, int h, int w, const float* field, int hf, int wf, int mode,
+                          const float* dout, int ld_out, int out_off, float* dinp, float* dfield, int N, int frames, float* ws,
+                          size_t ws_floats, void* stream) {
     MNK_REQUIRE(inp && field && dout && N > 0 && C > 0 && h > 0 && w > 0 && hf > 0 && wf > 0 && (mode == 0 || mode == 1));
     MNK_REQUIRE(ld_in % 4 == 0 && ld_in >= round_up(C, 4) && out_off >= 0 && out_off + C <= ld_out);
     MNK_REQUIRE(dinp || dfield);
     WarpSegs a = {};
-    a.n = 1, a.N = N, a.hf = hf, a.wf = wf, a.mode = mode;
+    a.n = 1, a.N = N, a.frames = frames, a.hf = hf, a.wf = wf, a.mode = mode;
     a.field = field, a.dfield = dfield, a.dfield_accumulate = 1;
     WarpSeg& L = a.lv[0];
     L.inp = inp, L.dout = dout, L.dinp = dinp, L.ld_in = ld_in, L.C = C, L.h = h, L.w = w, L.ld_out = ld_out, L.out_off = out_off;
     return warp_bwd_launch(a, ws, ws_floats, (double)N * h * w * C * 12, (hipStream_t)stream);
+}
+
+int mnk_deform_bwd(const float* inp, int ld_in, int C, int h, int w, const float* field, int hf, int wf, int mode,
+                   const float* dout, int ld_out, int out_off, float* dinp, float* dfield, int N, float* ws, size_t ws_floats,
+                   void* stream) {
+    return mnk_deform_shared_bwd(inp, ld_in, C, h, w, field, hf, wf, mode, dout, ld_out, out_off, dinp, dfield, N, 1, ws,
+                                 ws_floats, stream);
 }
 
 static int warp_levels_check(const MnkWarpLevel* lv, int n, const float* field, int hf, int wf, int mode, int He, int We,
@@ -1812,11 +1839,12 @@ static int warp_levels_check(const MnkWarpLevel* lv, int n, const float* field, 
     return MNK_OK;
 }
 
-int mnk_warp_levels_fwd(const MnkWarpLevel* levels, int nlevels, const float* field, int hf, int wf, int mode, const float* emb,
-                        int ld_emb, int He, int We, int N, void* stream) {
+int mnk_warp_levels_shared_fwd(const MnkWarpLevel* levels, int nlevels, const float* field, int hf, int wf, int mode,
+                               const float* emb, int ld_emb, int He, int We, int N, int frames, void* stream) {
     if (int rc = warp_levels_check(levels, nlevels, field, hf, wf, mode, He, We, ld_emb, N)) return rc;
+    if (int rc = warp_frames_check(N, frames)) return rc;
     WarpSegs a = {};
-    a.n = nlevels, a.N = N, a.hf = hf, a.wf = wf, a.mode = mode, a.ld_emb = ld_emb, a.He = He, a.We = We;
+    a.n = nlevels, a.N = N, a.frames = frames, a.hf = hf, a.wf = wf, a.mode = mode, a.ld_emb = ld_emb, a.He = He, a.We = We;
     a.field = field, a.emb = emb;
     int blocks = 0;
     double bytes = 0;
@@ -1843,6 +1871,11 @@ int mnk_warp_levels_fwd(const MnkWarpLevel* levels, int nlevels, const float* fi
     return MNK_OK;
 }
 
+int mnk_warp_levels_fwd(const MnkWarpLevel* levels, int nlevels, const float* field, int hf, int wf, int mode, const float* emb,
+                        int ld_emb, int He, int We, int N, void* stream) {
+    return mnk_warp_levels_shared_fwd(levels, nlevels, field, hf, wf, mode, emb, ld_emb, He, We, N, 1, stream);
+}
+
 size_t mnk_warp_levels_bwd_workspace_floats(const MnkWarpLevel* levels, int nlevels, int N) {
     if (!levels || nlevels <= 0 || nlevels > MAX_WARP_LEVELS || N <= 0) return 0;
     size_t need = 0;
@@ -1853,11 +1886,12 @@ size_t mnk_warp_levels_bwd_workspace_floats(const MnkWarpLevel* levels, int nlev
     return need;
 }
 
-int mnk_warp_levels_bwd(const MnkWarpLevel* levels, int nlevels, const float* field, int hf, int wf, int mode, float* dfield,
-                        float* demb, int ld_emb, int He, int We, int N, float* ws, size_t ws_floats, void* stream) {
+int mnk_warp_levels_shared_bwd(const MnkWarpLevel* levels, int nlevels, const float* field, int hf, int wf, int mode,
+                               float* dfield, float* demb, int ld_emb, int He, int We, int N, int frames, float* ws,
+                               size_t ws_floats, void* stream) {
     if (int rc = warp_levels_check(levels, nlevels, field, hf, wf, mode, He, We, ld_emb, N)) return rc;
     WarpSegs a = {};
-    a.n = nlevels, a.N = N, a.hf = hf, a.wf = wf, a.mode = mode, a.ld_emb = ld_emb, a.He = He, a.We = We;
+    a.n = nlevels, a.N = N, a.frames = frames, a.hf = hf, a.wf = wf, a.mode = mode, a.ld_emb = ld_emb, a.He = He, a.We = We;
     a.field = field, a.dfield = dfield, a.demb = demb, a.dfield_accumulate = 0;
     double bytes = 0;
     for (int l = 0; l < nlevels; ++l) {
@@ -1869,5 +1903,11 @@ int mnk_warp_levels_bwd(const MnkWarpLevel* levels, int nlevels, const float* fi
         bytes += (double)N * m.h * m.w * m.C * 12;
     }
     return warp_bwd_launch(a, ws, ws_floats, bytes, (hipStream_t)stream);
+}
+
+int mnk_warp_levels_bwd(const MnkWarpLevel* levels, int nlevels, const float* field, int hf, int wf, int mode, float* dfield,
+                        float* demb, int ld_emb, int He, int We, int N, float* ws, size_t ws_floats, void* stream) {
+    return mnk_warp_levels_shared_bwd(levels, nlevels, field, hf, wf, mode, dfield, demb, ld_emb, He, We, N, 1, ws, ws_floats,
+                                      stream);
 }
 }

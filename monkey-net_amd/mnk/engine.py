@@ -634,11 +634,14 @@ class Transfer:
     """transfer.py:65-79 transfer_one without its per-frame Python loops: ONE key-point detector call over all driving
     frames (the detector folds the time axis into the batch), normalize_kp on the device, and ONE generator call with the
     (video, frame) pairs folded into the batch.  Eval mode (running BatchNorm statistics), so frames are independent.
-    Returns the dict transfer_one returns."""
+    Returns the dict transfer_one returns.  shared_source=True hands the generator the B source images and the (B, d)
+    key points as they are: the appearance encoder runs once per source instead of once per frame, and its skip tensors
+    exist once (B instead of B*d rows); False repeats the source d times along the batch axis."""
 
-    def __init__(self, kp_detector, generator, normalization_params):
+    def __init__(self, kp_detector, generator, normalization_params, shared_source=False):
         self.kp_detector, self.generator = kp_detector.eval(), generator.eval()
         self.params = dict(normalization_params)
+        self.shared_source = bool(shared_source)
 
     @torch.no_grad()
     def __call__(self, source_image, driving_video):
@@ -646,6 +649,10 @@ class Transfer:
         kp_driving = self.kp_detector(driving_video)                     # (B, d, K, .)
         kp_source = self.kp_detector(source_image)                       # (B, 1, K, .)
         kp_norm = normalize_kp(kp_driving, kp_source, **self.params)
+        if self.shared_source:
+            out = self.generator(source_image, kp_driving=kp_norm, kp_source=kp_source)          # both (B, C, d, H, W)
+            return {"video_prediction": out["video_prediction"], "video_deformed": out["video_deformed"],
+                    "kp_driving": kp_driving, "kp_source": kp_source, "kp_norm": kp_norm}
         fold = lambda t: t.reshape((b * d, 1) + t.shape[2:])             # frame f of video v -> batch entry v * d + f
         rep = lambda t: t.repeat_interleave(d, dim=0)
         out = self.generator(rep(source_image), kp_driving={k: fold(v) for k, v in kp_norm.items()},

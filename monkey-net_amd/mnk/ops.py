@@ -125,11 +125,12 @@ class ToActFn(_Fn):
     @staticmethod
     def backward(ctx, g):
         b, c, d, h, w, step = ctx.meta
-        if step != 1:
-            raise NotImplementedError("gradient w.r.t. a down-scaled input image is never consumed by the reference")
         g = g.contiguous()
         out = torch.empty(b, c, d, h, w, dtype=torch.float32, device=g.device)
-        _call("mnk_nhwc_to_ncdhw", g, _p(g), g.shape[-1], _p(out), b, c, d, h, w)
+        if step != 1:     # the nearest down-scaling picks x[..., ::step, ::step]: its adjoint fills the other pixels with 0
+            _call("mnk_nhwc_to_ncdhw_strided", g, _p(g), g.shape[-1], _p(out), b, c, d, h, w, step)
+        else:
+            _call("mnk_nhwc_to_ncdhw", g, _p(g), g.shape[-1], _p(out), b, c, d, h, w)
         return out, None
 
 
@@ -1752,7 +1753,13 @@ class MovementEmbeddingFn(_Fn):
             g_var_s = gvs.view(b, d, k, 2, 2).sum(dim=1, keepdim=True) if d > 1 else gvs.view(b, 1, k, 2, 2)
             if not use_heatmap:
                 g_var_d = g_var_s = None
-        return None, g_mean_d, g_var_d, g_mean_s, g_var_s, None
+        g_img = None
+        if img is not None and use_deformed and ctx.needs_input_grad[0]:
+            # (no caller of the reference asks for it -- source images are data: a launch of its own, only when somebody does)
+            g_img = torch.empty_like(img)
+            _call("mnk_movement_embedding_img_bwd", dout, img.shape[-1], cimg, _p(mean_d), _p(mean_s), b, d, h, w, k, int(add_bg),
+                  int(use_heatmap), int(use_difference), _p(dout), dout.shape[-1], _p(g_img))
+        return g_img, g_mean_d, g_var_d, g_mean_s, g_var_s, None
 
 
 class MotionFieldKPFn(_Fn):
@@ -1812,20 +1819,49 @@ class MotionFieldFn(_Fn):
         return dpred, (ddelta if delta is not None else None), None, None, None
 
 
+def _warp_frames(field, inp):
+    """driving frames per source image: the field has rows v*frames + f, the source one image per video (generator.py:51-58
+    repeats the source along the depth axis instead)"""
+    n, m = field.shape[0], inp.shape[0]
+    if m <= 0 or n % m:
+        raise ValueError("warp: %d field rows cannot share %d source images" % (n, m))
+    return n // m
+
+
+def _deform_fwd(inp, ld_in, c, h, w, field, hf, wf, mode, out, n, frames):
+    if frames == 1:
+        _call("mnk_deform_fwd", inp, _p(inp), ld_in, c, h, w, _p(field), hf, wf, mode, _p(out), out.shape[-1], 0, n)
+    else:
+        _call("mnk_deform_shared_fwd", inp, _p(inp), ld_in, c, h, w, _p(field), hf, wf, mode, _p(out), out.shape[-1], 0, n,
+              frames)
+
+
+def _deform_bwd(inp, ld_in, c, h, w, field, hf, wf, mode, dout, dinp, dfield, n, frames):
+    nws = _query("mnk_deform_bwd_workspace_floats", c, h, w, n)         # (n: the field's rows, whatever the source has)
+    if frames == 1:
+        _call("mnk_deform_bwd", inp, _p(inp), ld_in, c, h, w, _p(field), hf, wf, mode, _p(dout), dout.shape[-1], 0,
+              _p(dinp), _p(dfield), n, _p(SCRATCH.get("ws", nws, inp)), nws)
+    else:
+        _call("mnk_deform_shared_bwd", inp, _p(inp), ld_in, c, h, w, _p(field), hf, wf, mode, _p(dout), dout.shape[-1], 0,
+              _p(dinp), _p(dfield), n, frames, _p(SCRATCH.get("ws", nws, inp)), nws)
+
+
 class WarpSkipFn(_Fn):
     """deform_input (generator.py:51-58) of one skip tensor, with the nearest-resized key-point embedding written
-    behind it in the same buffer (generator.py:72-73): out = [warp(inp, field) | resize(emb)]."""
+    behind it in the same buffer (generator.py:72-73): out = [warp(inp, field) | resize(emb)].  A source with fewer rows than
+    the field is shared by the frames of its video (_warp_frames): out has the field's rows, d input the source's shape."""
 
     @staticmethod
     def forward(ctx, inp, field, emb, c, ke, mode):
         _check_device(inp)
-        n, h, w, ld_in = inp.shape
-        _, hf, wf, _ = field.shape
+        _, h, w, ld_in = inp.shape
+        n, hf, wf, _ = field.shape
+        frames = _warp_frames(field, inp)
         # c a multiple of 4: the warp writes whole channel quads and the resized embedding, copied with its (zero) pad
         # channels, the rest of every pixel row -- no zero fill of the output
         whole = c % 4 == 0 and (emb is None or emb.shape[-1] == ceil4(ke))
         out = (torch.empty if whole else torch.zeros)(n, h, w, ceil4(c + ke), dtype=torch.float32, device=inp.device)
-        _call("mnk_deform_fwd", inp, _p(inp), ld_in, c, h, w, _p(field), hf, wf, mode, _p(out), out.shape[-1], 0, n)
+        _deform_fwd(inp, ld_in, c, h, w, field, hf, wf, mode, out, n, frames)
         if emb is not None:
             _call("mnk_resize_nearest" if mode == 0 else "mnk_resize_bilinear", inp, _p(emb), emb.shape[-1], emb.shape[1], emb.shape[2], _p(out), out.shape[-1], c,
                   h, w, n, ceil4(ke) if whole else ke)
@@ -1838,14 +1874,12 @@ class WarpSkipFn(_Fn):
         inp, field, emb = ctx.saved_tensors
         c, ke, mode = ctx.meta
         dout = dout.contiguous()
-        n, h, w, ld_in = inp.shape
-        _, hf, wf, _ = field.shape
+        _, h, w, ld_in = inp.shape
+        n, hf, wf, _ = field.shape
         dinp = torch.empty_like(inp) if ctx.needs_input_grad[0] else None       # written by the gather pass
         dfield = torch.zeros_like(field) if ctx.needs_input_grad[1] else None    # added to
         if dinp is not None or dfield is not None:
-            nws = _query("mnk_deform_bwd_workspace_floats", c, h, w, n)
-            _call("mnk_deform_bwd", inp, _p(inp), ld_in, c, h, w, _p(field), hf, wf, mode, _p(dout), dout.shape[-1], 0,
-                  _p(dinp), _p(dfield), n, _p(SCRATCH.get("ws", nws, inp)), nws)
+            _deform_bwd(inp, ld_in, c, h, w, field, hf, wf, mode, dout, dinp, dfield, n, _warp_frames(field, inp))
         demb = None
         if emb is not None and ctx.needs_input_grad[2]:
             # nearest: the adjoint is a gather that writes every source pixel; with c a multiple of 4 it also reads the
@@ -1871,31 +1905,35 @@ class WarpAllFn(_Fn):
     @staticmethod
     def forward(ctx, field, emb, mode, specs, *inps):
         _check_device(field)
-        _, hf, wf, _ = field.shape
+        n, hf, wf, _ = field.shape
+        frames = _warp_frames(field, inps[0])
+        if any(inp.shape[0] != inps[0].shape[0] for inp in inps):
+            raise ValueError("warp: the levels differ in their number of source images")
         outs = []
         ctx.multi = len(inps) <= 12 and knobs.form("WARP_LEVELS")
         if ctx.multi:         # one launch for the warps and embedding copies of all levels (mnk_warp_levels_fwd)
             lv = np.zeros(len(inps), dtype=WARP_LEVEL)
             for i, (inp, (c, ke)) in enumerate(zip(inps, specs)):
-                n, h, w, ld_in = inp.shape
+                _, h, w, ld_in = inp.shape
                 e = emb if ke else None
                 # (the launch writes every channel of every row -- warp, embedding, pad channels: no zero fill)
                 out = torch.empty(n, h, w, ceil4(c + ke), dtype=torch.float32, device=inp.device)
                 lv[i] = (inp.data_ptr(), out.data_ptr(), 0, 0, ld_in, c, h, w, out.shape[-1], ke if e is not None else 0, c, 0)
                 outs.append(out)
-            _call("mnk_warp_levels_fwd", field, lv.ctypes.data, len(inps), _p(field), hf, wf, mode, _p(emb),
-                  emb.shape[-1] if emb is not None else 0, emb.shape[1] if emb is not None else 0,
-                  emb.shape[2] if emb is not None else 0, inps[0].shape[0])
+            tail = (n,) if frames == 1 else (n, frames)
+            _call("mnk_warp_levels_fwd" if frames == 1 else "mnk_warp_levels_shared_fwd", field, lv.ctypes.data, len(inps),
+                  _p(field), hf, wf, mode, _p(emb), emb.shape[-1] if emb is not None else 0,
+                  emb.shape[1] if emb is not None else 0, emb.shape[2] if emb is not None else 0, *tail)
             ctx.save_for_backward(field, emb, *inps)
             ctx.meta = (mode, tuple(specs))
             ctx.set_materialize_grads(False)
             return tuple(outs)
         for inp, (c, ke) in zip(inps, specs):
-            n, h, w, ld_in = inp.shape
+            _, h, w, ld_in = inp.shape
             e = emb if ke else None
             whole = c % 4 == 0 and (e is None or e.shape[-1] == ceil4(ke))      # see WarpSkipFn.forward
             out = (torch.empty if whole else torch.zeros)(n, h, w, ceil4(c + ke), dtype=torch.float32, device=inp.device)
-            _call("mnk_deform_fwd", inp, _p(inp), ld_in, c, h, w, _p(field), hf, wf, mode, _p(out), out.shape[-1], 0, n)
+            _deform_fwd(inp, ld_in, c, h, w, field, hf, wf, mode, out, n, frames)
             if e is not None:
                 _call("mnk_resize_nearest" if mode == 0 else "mnk_resize_bilinear", inp, _p(e), e.shape[-1], e.shape[1],
                       e.shape[2], _p(out), out.shape[-1], c, h, w, n, ceil4(ke) if whole else ke)
@@ -1910,7 +1948,8 @@ class WarpAllFn(_Fn):
         field, emb = ctx.saved_tensors[:2]
         inps = ctx.saved_tensors[2:]
         mode, specs = ctx.meta
-        _, hf, wf, _ = field.shape
+        nrows, hf, wf, _ = field.shape
+        frames = _warp_frames(field, inps[0])
         # the gradients of all warps (d input of every level, d field) are slices of ONE buffer.  The acts come first (their
         # sizes are multiples of 4 floats: every slice stays 16-byte aligned for the float4 readers downstream), the field
         # last.  The one-launch form writes every element; the per-level form adds the levels' field gradients up.
@@ -1932,16 +1971,18 @@ class WarpAllFn(_Fn):
                 inp, (c, ke) = inps[i], specs[i]
                 dout = douts[i].contiguous()
                 keep.append(dout)
-                n, h, w, ld_in = inp.shape
+                _, h, w, ld_in = inp.shape
                 dinps[i] = flat[offs[i]:offs[i] + sizes[i]].view_as(inp) if want[i] else None
                 lv[j] = (inp.data_ptr(), 0, dout.data_ptr(), dinps[i].data_ptr() if dinps[i] is not None else 0, ld_in, c, h, w,
                          dout.shape[-1], ke if want_emb else 0, c, 0)
             if want_emb:
                 demb = torch.empty_like(emb)
-            nws = _query("mnk_warp_levels_bwd_workspace_floats", lv.ctypes.data, len(live), inps[0].shape[0])
-            _call("mnk_warp_levels_bwd", field, lv.ctypes.data, len(live), _p(field), hf, wf, mode, _p(dfield), _p(demb),
-                  emb.shape[-1] if emb is not None else 0, emb.shape[1] if emb is not None else 0,
-                  emb.shape[2] if emb is not None else 0, inps[0].shape[0], _p(SCRATCH.get("ws", nws, field)), nws)
+            nws = _query("mnk_warp_levels_bwd_workspace_floats", lv.ctypes.data, len(live), nrows)    # (the field's rows)
+            tail = (nrows,) if frames == 1 else (nrows, frames)
+            _call("mnk_warp_levels_bwd" if frames == 1 else "mnk_warp_levels_shared_bwd", field, lv.ctypes.data, len(live),
+                  _p(field), hf, wf, mode, _p(dfield), _p(demb), emb.shape[-1] if emb is not None else 0,
+                  emb.shape[1] if emb is not None else 0, emb.shape[2] if emb is not None else 0, *tail,
+                  _p(SCRATCH.get("ws", nws, field)), nws)
             return (dfield, demb, None, None) + tuple(dinps)
         if dfield is not None:
             dfield.zero_()
@@ -1950,12 +1991,11 @@ class WarpAllFn(_Fn):
                 dinps.append(None)
                 continue
             dout = dout.contiguous()
-            n, h, w, ld_in = inp.shape
+            _, h, w, ld_in = inp.shape
+            n = nrows
             dinp = flat[offs[i]:offs[i] + sizes[i]].view_as(inp) if want[i] else None
             if dinp is not None or dfield is not None:
-                nws = _query("mnk_deform_bwd_workspace_floats", c, h, w, n)
-                _call("mnk_deform_bwd", inp, _p(inp), ld_in, c, h, w, _p(field), hf, wf, mode, _p(dout), dout.shape[-1], 0,
-                      _p(dinp), _p(dfield), n, _p(SCRATCH.get("ws", nws, inp)), nws)
+                _deform_bwd(inp, ld_in, c, h, w, field, hf, wf, mode, dout, dinp, dfield, n, frames)
             dinps.append(dinp)
             if ke and emb is not None and ctx.needs_input_grad[1]:
                 # the first contribution writes demb (nearest: a gather over the source pixels that, with c a multiple of 4,

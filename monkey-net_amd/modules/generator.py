@@ -12,8 +12,10 @@ _MODES = {'nearest': 0, 'trilinear': 1}
 
 
 class MotionTransferGenerator(nn.Module):
-    """Given key-points and a source frame, reconstruct the driving frame.  Returns the refined prediction and the
-    purely warped source (generator.py:10-82)."""
+    """Given key-points and a source frame, reconstruct the driving frames.  Returns the refined prediction and the
+    purely warped source (generator.py:10-82), both (B, C, d, H, W) for d driving frames per source: the source is encoded
+    once (B rows), the field, the embedding, the decoder and the refinement run on the B*d rows v*d + f, and the warps read
+    source row v for every frame of video v (the reference's grid_sample over a depth-1 volume, generator.py:51-58)."""
 
     def __init__(self, num_channels, num_kp, kp_variance, block_expansion, max_features, num_blocks, num_refinement_blocks,
                  dense_motion_params=None, kp_embedding_params=None, interpolation_mode='nearest'):
@@ -54,8 +56,8 @@ class MotionTransferGenerator(nn.Module):
         """Public form of generator.py:51-58: inp (B,C,1,h,w), field (B,d,ho,wo,3) -> (B,C,d,h,w)."""
         b, c = inp.shape[:2]
         _, d, ho, wo, _ = deformations_absolute.shape
-        if d != 1:
-            raise NotImplementedError("the generator is only ever called with one driving frame (SURVEY.md app. A.15)")
+        if inp.shape[2] != 1:
+            raise NotImplementedError("deform_input takes one source frame per video; got %d" % inp.shape[2])
         field = deformations_absolute[..., :2].reshape(b * d, ho, wo, 2).contiguous()
         out = ops.WarpSkipFn.apply(ops.to_act(inp), field, None, c, 0, self._mode())
         return ops.from_act(out, c, b)
@@ -63,19 +65,21 @@ class MotionTransferGenerator(nn.Module):
     def forward(self, source_image, kp_driving, kp_source):
         b = source_image.shape[0]
         d = kp_driving['mean'].shape[1]
-        if d != 1 or source_image.shape[2] != 1:
-            raise NotImplementedError("the generator is only ever called with one source and one driving frame "
-                                      "(train.py:38, reconstruction.py:15-17, transfer.py:72-74)")
+        if d < 1 or source_image.shape[2] != 1:
+            raise NotImplementedError("the generator takes one source frame per video (train.py:38, reconstruction.py:15-17, "
+                                      "transfer.py:72-74) and d >= 1 driving frames; got %d source frames, d = %d"
+                                      % (source_image.shape[2], d))
         mode = self._mode()
         src_act = ops.to_act(source_image)
         # (the appearance encoder does not depend on the key points; running it as a second-stream branch next to the
         # dense-motion network was measured at 11.46 vs 11.44 ms per step -- every kernel fills the chip -- and removed)
         skips = self.appearance_encoder.forward_act(src_act, self.num_channels)
-        field = self.dense_motion_module.field_act(source_image, kp_driving, kp_source)     # (B,hf,wf,2)
+        field = self.dense_motion_module.field_act(source_image, kp_driving, kp_source)     # (B*d,hf,wf,2)
         emb, ke = None, 0
         if self.kp_embedding_module is not None:
             emb, ke = self.kp_embedding_module.forward_act(source_image, kp_driving, kp_source)
-        # all warps of this forward as one autograd node: one shared field-gradient buffer (ops.WarpAllFn)
+        # all warps of this forward as one autograd node: one shared field-gradient buffer (ops.WarpAllFn); the B source
+        # rows are shared by the d frames of their video, the outputs have B*d rows
         specs = tuple((c, ke) for _, c in skips) + ((self.num_channels, 0),)
         outs = ops.WarpAllFn.apply(field, emb, mode, specs, *([a for a, _ in skips] + [src_act]))
         warped = [(o, c + ke) for o, (_, c) in zip(outs[:-1], skips)]

@@ -36,7 +36,7 @@ class MovementEmbeddingModule(nn.Module):
         d, k = kp_driving['mean'].shape[1:3]
         img = None
         if self.use_deformed_source_image:
-            img = src_act if src_act is not None else ops.to_act(source_image.detach(), step)
+            img = src_act if src_act is not None else ops.to_act(source_image, step)
         var_d, const_var = _split_variance(kp_driving, self.kp_variance) if self.use_heatmap else (None, 1.0)
         var_s, _ = _split_variance(kp_source, self.kp_variance) if self.use_heatmap else (None, 1.0)
         cfg = (b, d, h, w, k, self.num_channels, bool(self.add_bg_feature_map), bool(self.use_heatmap),
