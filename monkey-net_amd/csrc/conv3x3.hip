@@ -24,6 +24,7 @@
 // with a deterministic second-pass reduction (no atomics), which also applies bias and the residual add.
 #include <stdlib.h>
 #include <string.h>
+#include <mutex>
 #include <type_traits>
 
 #include "conv_common.h"
@@ -91,6 +92,61 @@ struct ConvArgs {
     int phases, tiles_per_phase;
     long phase_wstride;
     BnBwdSrc bnb;
+    // ---- position-major launches (the PM kernels; conv2d_fwd_impl decides) --------------------------------------------------
+    unsigned mulF, shF;     // division of a GEMM row by the frame count N (fast_div)
+    unsigned mulKW, shKW;   // division of a tap index by kw
+};
+
+// GEMM row -> output pixel.  Frame-major (the memory order): m = (fr * H + h) * W + w -- 64 consecutive rows of a small map
+// cover every position, so every tap is inside the source for SOME row of a tile.  Position-major: m = (h * W + w) * N + fr --
+// the rows of a tile share one position (N >= BM) or BM / N neighbouring ones, and a tap that falls into the padding does so
+// for the whole tile: the block leaves its K steps out (TapCursor).  Only the row <-> pixel map of the launch changes; every
+// tensor, and the split-K workspace [split][phase][M][ldw], keeps its frame-major memory order.
+template <bool PM>
+__device__ __forceinline__ void row_pixel(const ConvArgs& a, unsigned m, unsigned& fr, unsigned& h, unsigned& w) {
+    if constexpr (PM) {
+        const unsigned p = fast_div(m, a.mulF, a.shF);
+        fr = m - p * (unsigned)a.N;
+        h = fast_div(p, a.mulW, a.shW);
+        w = p - h * (unsigned)a.W;
+    } else {
+        const unsigned tt = fast_div(m, a.mulW, a.shW);
+        fr = fast_div(tt, a.mulH, a.shH);
+        w = m - tt * (unsigned)a.W;
+        h = tt - fr * (unsigned)a.H;
+    }
+}
+
+// K cursor of a tap-skipping block: walks the steps s = chunk * ntaps + tap whose tap bit is set in the block's mask (bit t: tap
+// t lies inside the source for at least one row of the tile), in step order, without divisions: the next set bit above the
+// current tap, or the lowest one of the next chunk.  Everything is wave-uniform (scalar registers).
+// A skipped step would have multiplied activations that are exactly zero: fma(0, w, acc) = acc for finite w, and the order of
+// the steps that remain, the split ranges and the two alternating accumulator sets are untouched -- every output keeps its
+// value (up to the sign of a zero).  A NON-FINITE weight is the exception: it used to poison the rows whose tap is outside
+// (0 * inf = NaN) and no longer does where the step is skipped.
+struct TapCursor {
+    unsigned mask;
+    int chunk, tap;
+    // first set step at or behind s (mask != 0)
+    __device__ __forceinline__ void seek(unsigned mask_, int s, int ntaps) {
+        mask = mask_;
+        chunk = s / ntaps;
+        const int t0 = s - chunk * ntaps;
+        const unsigned rem = mask >> t0;
+        tap = rem ? t0 + __builtin_ctz(rem) : __builtin_ctz(mask);
+        chunk += rem ? 0 : 1;
+    }
+    __device__ __forceinline__ void next() {
+        const unsigned rem = (mask >> tap) >> 1;
+        tap = rem ? tap + 1 + __builtin_ctz(rem) : __builtin_ctz(mask);
+        chunk += rem ? 0 : 1;
+    }
+    // set steps in [s0, s1)
+    __device__ __forceinline__ static int count(unsigned mask, int s0, int s1, int ntaps) {
+        const int c0 = s0 / ntaps, t0 = s0 - c0 * ntaps, c1 = s1 / ntaps, t1 = s1 - c1 * ntaps;
+        return (c1 - c0) * __builtin_popcount(mask) + __builtin_popcount(mask & ((1u << t1) - 1u)) -
+               __builtin_popcount(mask & ((1u << t0) - 1u));
+    }
 };
 
 // ---- the activation-side loader of the implicit GEMM (shared by the 32x32 and 16x16 tile kernels) -------------------
@@ -186,7 +242,10 @@ struct ActLoader {
 // (offsets stay far below 2^30; num_records = 2^30): an out-of-image tap or a chunk beyond the channel count gets bit
 // 30 added to its offset and the hardware returns zeros -- no clamping, no data masks, no branches.  Per row and step:
 // one add, one bit-field extract, one and-or (+ five for the parity shifts of the nearest x2 up-sampling view).
-template <int RA, bool UPS, int NST = 1>
+// PM: the rows are position-major (row_pixel) and the K cursor is `cur`, which the kernel points at the block's first step
+// (TapCursor).  The rows of such a tile lie a whole frame apart, so the buffer window starts at the tensor (the host checks
+// that the sources fit it).
+template <int RA, bool UPS, int NST = 1, bool PM = false>
 struct ActLoader3 {
     unsigned b0[RA], b1[RA];       // byte offset of the row's centre pixel in source 0 / 1 (relative to the block base)
     unsigned inv[RA];              // bit t: tap t lies outside the image
@@ -194,16 +253,28 @@ struct ActLoader3 {
     float4 ra[NST][RA];
     __amdgpu_buffer_rsrc_t r0, r1;
     int chunk, ky, kx, Ws, lq4;
+    TapCursor cur;
+
+    // taps that are outside for EVERY row this thread loads
+    __device__ __forceinline__ unsigned inv_all() const {
+        unsigned v = inv[0];
+#pragma unroll
+        for (int j = 1; j < RA; ++j) v &= inv[j];
+        return v;
+    }
 
     __device__ __forceinline__ void setup(const ConvArgs& a, long m0, int lrow, int lq_, int s_begin, int, int) {
         lq4 = lq_ * 16;
         const int Hs = UPS ? a.Hi >> 1 : a.Hi;
         Ws = UPS ? a.Wi >> 1 : a.Wi;
-        const unsigned mb = (unsigned)(m0 < a.M ? m0 : a.M - 1), tb = fast_div(mb, a.mulW, a.shW),
-                       fb = fast_div(tb, a.mulH, a.shH);
-        const long rowidx0 = (long)fb * Hs + ((int)(tb - fb * (unsigned)a.H) >> (UPS ? 1 : 0));
-        long pbase = rowidx0 * Ws - Ws - 1;
-        if (pbase < 0) pbase = 0;
+        long pbase = 0;            // position-major: the window starts at the tensor
+        if constexpr (!PM) {
+            const unsigned mb = (unsigned)(m0 < a.M ? m0 : a.M - 1), tb = fast_div(mb, a.mulW, a.shW),
+                           fb = fast_div(tb, a.mulH, a.shH);
+            const long rowidx0 = (long)fb * Hs + ((int)(tb - fb * (unsigned)a.H) >> (UPS ? 1 : 0));
+            pbase = rowidx0 * Ws - Ws - 1;
+            if (pbase < 0) pbase = 0;
+        }
         r0 = __builtin_amdgcn_make_buffer_rsrc((void*)(a.x0 + pbase * a.ld0), 0, 0x40000000, 0x00020000);
         r1 = __builtin_amdgcn_make_buffer_rsrc((void*)((a.x1 ? a.x1 : a.x0) + pbase * (a.x1 ? a.ld1 : a.ld0)), 0, 0x40000000,
                                                0x00020000);
@@ -211,8 +282,9 @@ struct ActLoader3 {
         for (int j = 0; j < RA; ++j) {
             long ml = m0 + lrow + 64 * j;
             if (ml > a.M - 1) ml = a.M - 1;
-            const unsigned m = (unsigned)ml, tt = fast_div(m, a.mulW, a.shW), fr = fast_div(tt, a.mulH, a.shH);
-            const int w = (int)(m - tt * (unsigned)a.W), h = (int)(tt - fr * (unsigned)a.H);
+            unsigned fr, hu, wu;
+            row_pixel<PM>(a, (unsigned)ml, fr, hu, wu);
+            const int w = (int)wu, h = (int)hu;
             const long rel = ((long)fr * Hs + (h >> (UPS ? 1 : 0))) * Ws + (w >> (UPS ? 1 : 0)) - pbase;
             b0[j] = (unsigned)(rel * a.ld0 * 4);
             b1[j] = (unsigned)(rel * a.ld1 * 4);
@@ -225,12 +297,18 @@ struct ActLoader3 {
             inv[j] = mk;
             par[j] = ((h & 1) ? 2u : 1u) | ((w & 1) ? 8u : 4u);
         }
+        if constexpr (PM) return;
         chunk = s_begin / 9;
         ky = (s_begin - chunk * 9) / 3;
         kx = (s_begin - chunk * 9) - ky * 3;
     }
     template <int ST = 0>
     __device__ __forceinline__ void load(const ConvArgs& a) {
+        if constexpr (PM) {
+            chunk = cur.chunk;
+            ky = (cur.tap * 11) >> 5;      // tap / 3 for tap < 9
+            kx = cur.tap - 3 * ky;
+        }
         const int c0 = chunk * BK;
         const bool second = c0 >= a.C0p;
         const int cbase = second ? c0 - a.C0p : c0;
@@ -260,6 +338,10 @@ struct ActLoader3 {
             off = ((unsigned)bad & 0x40000000u) | off;
             ra[ST][j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
         }
+        if constexpr (PM) {
+            cur.next();
+            return;
+        }
         const int kx1 = kx + 1;
         const bool wx = kx1 == 3;
         kx = wx ? 0 : kx1;
@@ -275,7 +357,7 @@ struct ActLoader3 {
 // ---- the same idea for any K x K kernel with stride 1 and padding `pad` (the discriminator's 4x4 / pad 0 forward and its
 // pad 3 data gradient), sources with clean pad channels, no up-sampled view: per-row base offset + one validity bit per
 // tap (K*K <= 32); an out-of-image tap or a channel chunk beyond C reads zeros through the buffer range check.
-template <int RA, int NST = 1>
+template <int RA, int NST = 1, bool PM = false>       // PM: see ActLoader3
 struct ActLoaderK {
     unsigned b0[RA], b1[RA];       // byte offset of input pixel (h * stride, w * stride) -- tap (pad_y, pad_x) -- relative to the
                                    // block base; may lie outside the image (pad > 0): it is only a base for the tap arithmetic
@@ -283,6 +365,14 @@ struct ActLoaderK {
     float4 ra[NST][RA];
     __amdgpu_buffer_rsrc_t r0, r1;
     int chunk, ky, kx, khh, lq4, pady, padx;
+    TapCursor cur;
+
+    __device__ __forceinline__ unsigned inv_all() const {
+        unsigned v = inv[0];
+#pragma unroll
+        for (int j = 1; j < RA; ++j) v &= inv[j];
+        return v;
+    }
 
     __device__ __forceinline__ void setup(const ConvArgs& a, long m0, int lrow, int lq_, int s_begin, int pad_y, int pad_x) {
         lq4 = lq_ * 16;
@@ -290,11 +380,14 @@ struct ActLoaderK {
         pady = pad_y;
         padx = pad_x;
         const int sd = a.stride;
-        const unsigned mb = (unsigned)(m0 < a.M ? m0 : a.M - 1), tb = fast_div(mb, a.mulW, a.shW),
-                       fb = fast_div(tb, a.mulH, a.shH);
-        // lowest address a valid tap of this block can have: input pixel (h0 * stride - pad_y, -pad_x) of the first row's frame
-        long pbase = ((long)fb * a.Hi + (int)(tb - fb * (unsigned)a.H) * sd - pad_y) * a.Wi - pad_x;
-        if (pbase < 0) pbase = 0;
+        long pbase = 0;            // position-major: the window starts at the tensor
+        if constexpr (!PM) {
+            const unsigned mb = (unsigned)(m0 < a.M ? m0 : a.M - 1), tb = fast_div(mb, a.mulW, a.shW),
+                           fb = fast_div(tb, a.mulH, a.shH);
+            // lowest address a valid tap of this block can have: input pixel (h0 * stride - pad_y, -pad_x) of the first row's frame
+            pbase = ((long)fb * a.Hi + (int)(tb - fb * (unsigned)a.H) * sd - pad_y) * a.Wi - pad_x;
+            if (pbase < 0) pbase = 0;
+        }
         r0 = __builtin_amdgcn_make_buffer_rsrc((void*)(a.x0 + pbase * a.ld0), 0, 0x40000000, 0x00020000);
         r1 = __builtin_amdgcn_make_buffer_rsrc((void*)((a.x1 ? a.x1 : a.x0) + pbase * (a.x1 ? a.ld1 : a.ld0)), 0, 0x40000000,
                                                0x00020000);
@@ -302,8 +395,9 @@ struct ActLoaderK {
         for (int j = 0; j < RA; ++j) {
             long ml = m0 + lrow + 64 * j;
             if (ml > a.M - 1) ml = a.M - 1;
-            const unsigned m = (unsigned)ml, tt = fast_div(m, a.mulW, a.shW), fr = fast_div(tt, a.mulH, a.shH);
-            const int w = (int)(m - tt * (unsigned)a.W) * sd, h = (int)(tt - fr * (unsigned)a.H) * sd;
+            unsigned fr, hu, wu;
+            row_pixel<PM>(a, (unsigned)ml, fr, hu, wu);
+            const int w = (int)wu * sd, h = (int)hu * sd;
             const long rel = ((long)fr * a.Hi + h) * a.Wi + w - pbase;
             b0[j] = (unsigned)(rel * a.ld0 * 4);
             b1[j] = (unsigned)(rel * a.ld1 * 4);
@@ -318,12 +412,18 @@ struct ActLoaderK {
             }
             inv[j] = mk;
         }
+        if constexpr (PM) return;
         chunk = s_begin / a.ntaps;
         ky = (s_begin - chunk * a.ntaps) / a.kw;
         kx = (s_begin - chunk * a.ntaps) - ky * a.kw;
     }
     template <int ST = 0>
     __device__ __forceinline__ void load(const ConvArgs& a) {
+        if constexpr (PM) {
+            chunk = cur.chunk;
+            ky = (int)fast_div((unsigned)cur.tap, a.mulKW, a.shKW);
+            kx = cur.tap - ky * a.kw;
+        }
         const int c0 = chunk * BK;
         const bool second = c0 >= a.C0p;
         const int cbase = second ? c0 - a.C0p : c0;
@@ -340,6 +440,10 @@ struct ActLoaderK {
             off = ((unsigned)bad & 0x40000000u) | off;
             ra[ST][j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
         }
+        if constexpr (PM) {
+            cur.next();
+            return;
+        }
         const int kx1 = kx + 1;
         const bool wx = kx1 == a.kw;
         kx = wx ? 0 : kx1;
@@ -352,10 +456,10 @@ struct ActLoaderK {
     __device__ __forceinline__ float4 masked(int j) const { return ra[ST][j]; }
 };
 
-template <int RA, int MODE, int NST = 1> struct LoaderSel { typedef ActLoader<RA, NST> type; };
-template <int RA, int NST> struct LoaderSel<RA, 3, NST> { typedef ActLoaderK<RA, NST> type; };
-template <int RA, int NST> struct LoaderSel<RA, 1, NST> { typedef ActLoader3<RA, false, NST> type; };
-template <int RA, int NST> struct LoaderSel<RA, 2, NST> { typedef ActLoader3<RA, true, NST> type; };
+template <int RA, int MODE, int NST = 1, bool PM = false> struct LoaderSel { typedef ActLoader<RA, NST> type; };
+template <int RA, int NST, bool PM> struct LoaderSel<RA, 3, NST, PM> { typedef ActLoaderK<RA, NST, PM> type; };
+template <int RA, int NST, bool PM> struct LoaderSel<RA, 1, NST, PM> { typedef ActLoader3<RA, false, NST, PM> type; };
+template <int RA, int NST, bool PM> struct LoaderSel<RA, 2, NST, PM> { typedef ActLoader3<RA, true, NST, PM> type; };
 
 #ifndef MNK_IGEMM_OCC
 #define MNK_IGEMM_OCC 3                       // waves per SIMD = blocks per CU the register budget is held to
@@ -388,8 +492,12 @@ constexpr int LDS_H = 24;     // padded LDS row of the bf16 planes (16 + 8 halve
 
 // GM: 0 -- v_mfma_f32_32x32x2_f32 on fp32 tiles; 1 -- the same products on the bf16 matrix cores: the loaders split every fp32
 // operand into three bf16 planes on its way to LDS and a K step of 16 is six v_mfma_f32_32x32x16_bf16 per tile (mnk_common.h)
-template <int BM, int BN, int WM, int WN, int MODE, int GM = 0>     // MODE: 0 generic loader, 1 / 2 the 3x3 fast loader (plain / x2 up-sampled)
+// PM: position-major rows + block-uniform tap skipping (row_pixel, TapCursor): fast loaders and fp32 products only, and only
+// launches whose epilogue leaves no per-block column sums -- those are fp32 sums over the rows of a tile, and another row
+// order would change their bits
+template <int BM, int BN, int WM, int WN, int MODE, int GM = 0, bool PM = false>     // MODE: 0 generic loader, 1 / 2 the 3x3 fast loader (plain / x2 up-sampled)
 __global__ void __launch_bounds__(256, MNK_IGEMM_OCC) conv3x3_igemm_kernel(ConvArgs a) {
+    static_assert(!PM || (MODE != 0 && GM == 0), "position-major rows: buffer-load loaders, fp32 products");
     MNK_PHASE(0);
     constexpr int RA = BM / 64;               // A rows per thread per K step
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
@@ -431,8 +539,23 @@ __global__ void __launch_bounds__(256, MNK_IGEMM_OCC) conv3x3_igemm_kernel(ConvA
 
     // ---- per-thread global->LDS assignment: row inside a 64-row slab, float4 column (4 channels) --------------
     const int lrow = t >> 2, lq = t & 3;
-    typename LoaderSel<RA, MODE, NST>::type L;
+    typename LoaderSel<RA, MODE, NST, PM>::type L;
     L.setup(a, m0, lrow, lq, s_begin, a.pad - pa, (a.pad_x < 0 ? a.pad : a.pad_x) - pb);
+    int n = s_end - s_begin;                  // K steps of this block
+    if constexpr (PM) {
+        // the tile's tap mask: a tap is skipped when it is outside for every row of every thread (rows beyond M repeat row M - 1)
+        __shared__ unsigned tap_red[4];
+        unsigned v = L.inv_all();
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v &= __shfl_xor(v, o);
+        if (lane == 0) tap_red[wave] = v;
+        __syncthreads();
+        v = tap_red[0] & tap_red[1] & tap_red[2] & tap_red[3];
+        const unsigned all_taps = a.ntaps >= 32 ? ~0u : (1u << a.ntaps) - 1u;
+        const unsigned mask = (unsigned)__builtin_amdgcn_readfirstlane((int)(~v & all_taps));
+        n = mask ? TapCursor::count(mask, s_begin, s_end, a.ntaps) : 0;
+        if (n > 0) L.cur.seek(mask, s_begin, a.ntaps);
+    }
     constexpr int RB = (BN + 63) / 64;        // B rows per thread per K step
     const long KT = (long)a.ksteps * BK;     // packed row length
     static_assert(RB <= 2, "at most two weight rows per thread");
@@ -445,6 +568,7 @@ __global__ void __launch_bounds__(256, MNK_IGEMM_OCC) conv3x3_igemm_kernel(ConvA
     // global loads of K step s into register stage ST (the activation loader keeps its own cursor: steps in order)
     auto load_step = [&](int s, auto st_tag) __attribute__((always_inline)) {
         constexpr int ST = decltype(st_tag)::value;
+        if constexpr (PM) s = L.cur.chunk * a.ntaps + L.cur.tap;      // the cursor's step: the steps in between are skipped
         L.template load<ST>(a);
         const float* wsrc_ptr = wpb + (long)s * BK;
         if constexpr (ST == 0) {
@@ -560,7 +684,6 @@ __global__ void __launch_bounds__(256, MNK_IGEMM_OCC) conv3x3_igemm_kernel(ConvA
     // branch-free (two steps per trip: LDS buffer and register stage are compile-time constants); the tail is peeled.
     // (Two steps per barrier -- four LDS buffers, half the barriers -- was built and measured in round 3: the per-layer
     // bench unchanged, the whole step 10.90 vs 10.79 ms with 40 KB of LDS per block: removed.  profiles/r03_knob_ab_log.txt)
-    const int n = s_end - s_begin;
     if (n > 0) {
         load_step(s_begin, St0{});
         store_step(0, St0{});
@@ -630,15 +753,17 @@ __global__ void __launch_bounds__(256, MNK_IGEMM_OCC) conv3x3_igemm_kernel(ConvA
     const bool full = m0 + BM <= a.M;             // every row of the tile is a real pixel: no per-row guards
     const unsigned mrow0 = (unsigned)m0 + wm * (BM / WM) + 4 * fk, Mu = (unsigned)a.M;
     const bool scatter = a.phases > 1 && !split_out;   // row m = (n, i, j) of the phase -> pixel (2i + pa, 2j + pb) of y
+    // GEMM row -> row of the output tensor (of the split-K partials: their own frame-major order)
     auto out_row = [&](unsigned m) __attribute__((always_inline)) -> unsigned {
-        if (!scatter) return m;
-        const unsigned tt = fast_div(m, a.mulW, a.shW), fr = fast_div(tt, a.mulH, a.shH);
-        const unsigned j = m - tt * (unsigned)a.W, i = tt - fr * (unsigned)a.H;
+        if (!PM && !scatter) return m;
+        unsigned fr, i, j;
+        row_pixel<PM>(a, m, fr, i, j);
+        if (PM && !scatter) return (fr * (unsigned)a.H + i) * (unsigned)a.W + j;
         return ((fr * (unsigned)a.H + i) * 2u + (unsigned)pa) * (2u * (unsigned)a.W) + 2u * j + (unsigned)pb;
     };
     int cov[TN];
     float bv[TN], s1[TN], s2[TN];
-    const bool bnb = a.bnb.y != nullptr && a.stats && !split_out;     // the column sums are a BatchNorm layer's backward statistics
+    const bool bnb = !PM && a.bnb.y != nullptr && a.stats && !split_out;     // the column sums are a BatchNorm layer's backward statistics
     float bm[TN], bis[TN], bsc[TN], bbe[TN];
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
@@ -669,7 +794,9 @@ __global__ void __launch_bounds__(256, MNK_IGEMM_OCC) conv3x3_igemm_kernel(ConvA
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
                             const unsigned ro = (r & 3) + 8 * (r >> 2);
-                            if (FULL || mb + ro < Mu) rv[r] = a.residual[roff0 + ro * (unsigned)a.ld_res];
+                            if (FULL || mb + ro < Mu)
+                                rv[r] = PM ? a.residual[out_row(mb + ro) * (unsigned)a.ld_res + (unsigned)co]
+                                           : a.residual[roff0 + ro * (unsigned)a.ld_res];
                         }
                     }
                     float yv[16];
@@ -687,7 +814,7 @@ __global__ void __launch_bounds__(256, MNK_IGEMM_OCC) conv3x3_igemm_kernel(ConvA
                         float v = acc[0][i][j][r];
                         if (!split_out) v = c_real ? (v + bv[j]) + rv[r] : 0.f;
                         if (FULL || mb + ro < Mu) {
-                            if (scatter)
+                            if (PM || scatter)
                                 obase[out_row(mb + ro) * ldo + (unsigned)co] = v;
                             else
                                 obase[off0 + ro * ldo] = v;
@@ -712,7 +839,7 @@ __global__ void __launch_bounds__(256, MNK_IGEMM_OCC) conv3x3_igemm_kernel(ConvA
         emit(FalseTag{});
     // ---- fused BatchNorm statistics of the tensor just written (sync_batchnorm/batchnorm.py:60-62): per-block
     // column sums -> stats[blockIdx.x][2][ld_y]; the tiny final reduction over blocks is mnk_bn_stats_finish.
-    if (a.stats && !split_out) {
+    if (!PM && a.stats && !split_out) {
         float* red = reinterpret_cast<float*>(smem_a);          // the main loop ended with a barrier: LDS is free
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
@@ -1496,6 +1623,97 @@ static Launch plan_launch(int ntaps, int phases, int N, int H, int W, int C0, in
     return l;
 }
 
+// ---- position-major rows + tap skipping (conv3x3_igemm_kernel<..., PM>) -----------------------------------------------------
+// 1: launches that can leave K steps out run position-major; 0: every launch keeps the frame-major order and all its steps
+static int g_ktap_skip = tuning_knob("ktap_skip", &g_ktap_skip, 1);
+// the least share of a launch's (row, tap) pairs, in per cent, that must fall away for the position-major order to be used.
+// Its rows lie a frame apart, so a tile re-reads nothing of its neighbours' halo, and the launch keeps the split count that
+// was chosen for the full K.  Measured per launch (profiles/tap_skip_ab.txt): the groups that lose 41 % and more got faster
+// (the discriminator's 2x2 -> 5x5 data gradient 38.8 -> 18.6 us, 2x2-map layers 14 ... 24 %, 10x10 -> 13x13 2 %); 3x3 layers
+// on 4x4 maps (31 %) came out level in sum, 8x8 (16 %) and 16x16 maps (8 %) level or slower, and the discriminator's
+// 27x27 -> 30x30 data gradient (19 %) 4 % slower: those keep the frame-major order
+static int g_ktap_skip_min = tuning_knob("ktap_skip_min", &g_ktap_skip_min, 35);
+
+// sum over the M tiles of a position-major launch (every phase) of rows(tile) * taps(tile), taps(tile) = the taps that lie inside
+// the source for at least one position of the tile: the (row, tap) pairs the launch issues -- M * phases * ntaps without skipping.
+// This is the PLAN's count, made on the host from the geometry with the rule the blocks apply to their own rows (the AND of
+// the rows' out-of-image bits); nothing is read back from the device.
+struct TapGeom {
+    int bm, N, H, W, Hi, Wi, kh, kw, pad, stride, phases;
+    bool operator==(const TapGeom& o) const {
+        return bm == o.bm && N == o.N && H == o.H && W == o.W && Hi == o.Hi && Wi == o.Wi && kh == o.kh && kw == o.kw &&
+               pad == o.pad && stride == o.stride && phases == o.phases;
+    }
+};
+static double count_row_taps(const TapGeom& g) {
+    const long M = (long)g.N * g.H * g.W;
+    double total = 0.0;
+    for (int phase = 0; phase < g.phases; ++phase) {
+        const int pad_y = g.pad - (phase >> 1), pad_x = g.pad - (phase & 1);
+        for (long m0 = 0; m0 < M; m0 += g.bm) {
+            const long m1 = m0 + g.bm < M ? m0 + g.bm : M;
+            unsigned mask = 0;
+            for (long p = m0 / g.N; p <= (m1 - 1) / g.N; ++p) {
+                const int h = (int)(p / g.W) * g.stride, w = (int)(p % g.W) * g.stride;
+                for (int ky = 0; ky < g.kh; ++ky)
+                    for (int kx = 0; kx < g.kw; ++kx) {
+                        const int hh = h + ky - pad_y, ww = w + kx - pad_x;
+                        if (hh >= 0 && hh < g.Hi && ww >= 0 && ww < g.Wi) mask |= 1u << (ky * g.kw + kx);
+                    }
+            }
+            total += (double)(m1 - m0) * __builtin_popcount(mask);
+        }
+    }
+    return total;
+}
+// the count of a geometry is remembered (a training step launches the same few dozen shapes again and again): a small table
+// under a lock, the oldest entry is replaced when it is full
+static double issued_row_taps(const TapGeom& g) {
+    constexpr int SLOTS = 128;
+    static std::mutex lock;
+    static TapGeom memo_g[SLOTS];
+    static double memo_v[SLOTS];
+    static int memo_n = 0, memo_next = 0;
+    {
+        std::lock_guard<std::mutex> hold(lock);
+        for (int i = 0; i < memo_n; ++i)
+            if (memo_g[i] == g) return memo_v[i];
+    }
+    const double total = count_row_taps(g);
+    std::lock_guard<std::mutex> hold(lock);
+    memo_g[memo_next] = g;
+    memo_v[memo_next] = total;
+    memo_next = (memo_next + 1) % SLOTS;
+    if (memo_n < SLOTS) ++memo_n;
+    return total;
+}
+
+// Does this launch run position-major?  Only the 32x32-tile fp32 kernels through a buffer-load loader have the form; the
+// sources must fit the loaders' window from the start of the tensor (the rows of a tile lie a frame apart); an unsplit launch
+// with a column-sum epilogue keeps the frame-major order (its sums are sums over a tile's rows; a split launch's sums come
+// from the reduction, which walks memory order); and the order must pay: ktap_skip_min.  *row_taps: the pairs it issues.
+static bool plan_taps(const Plan& p, int mode, bool column_sums, const TapGeom& g, long src_bytes, double* row_taps) {
+    const double all = (double)g.N * g.H * g.W * g.phases * g.kh * g.kw;
+    *row_taps = all;
+    if (!g_ktap_skip || g_gemm_bf16x3 || p.bn == 16 || p.bn == 48 || mode < 1 || mode > 3) return false;
+    if (column_sums || src_bytes >= (1L << 29) || g.kh * g.kw > 32) return false;
+    // no tile order can skip more than the (position, tap) pairs that are outside: a product of two one-dimensional counts
+    double inside = 0.0;
+    for (int phase = 0; phase < g.phases; ++phase) {
+        long vy = 0, vx = 0;
+        for (int h = 0; h < g.H; ++h)
+            for (int ky = 0; ky < g.kh; ++ky) vy += h * g.stride + ky - (g.pad - (phase >> 1)) >= 0 && h * g.stride + ky - (g.pad - (phase >> 1)) < g.Hi;
+        for (int w = 0; w < g.W; ++w)
+            for (int kx = 0; kx < g.kw; ++kx) vx += w * g.stride + kx - (g.pad - (phase & 1)) >= 0 && w * g.stride + kx - (g.pad - (phase & 1)) < g.Wi;
+        inside += (double)vy * (double)vx * g.N;
+    }
+    if ((all - inside) * 100.0 < all * (double)g_ktap_skip_min) return false;
+    const double issued = issued_row_taps(g);
+    if (issued >= all || (all - issued) * 100.0 < all * (double)g_ktap_skip_min) return false;
+    *row_taps = issued;
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1574,6 +1792,7 @@ struct IgemmLaunch {
     hipStream_t s;
     bool timed;               // the roofline kernel is timed by its own begin / end stamps
     hipEvent_t ev0, ev1;
+    bool pm;                  // the position-major, tap-skipping instantiation (plan_taps)
 };
 static void launch_igemm(void (*kernel)(ConvArgs), const IgemmLaunch& L, const ConvArgs& a) {
     if (L.timed) hipExtLaunchKernelGGL(kernel, L.grid, dim3(256), 0, L.s, L.ev0, L.ev1, 0, a);
@@ -1582,6 +1801,14 @@ static void launch_igemm(void (*kernel)(ConvArgs), const IgemmLaunch& L, const C
 // the 32x32-MFMA kernel of a tile / the 16x16-MFMA kernel of a width, by loader mode; GM: 1 = bf16x3 products
 template <int BM, int BN, int WM, int WN, int GM>
 static void launch_tile(int mode, const IgemmLaunch& L, const ConvArgs& a) {
+    if constexpr (GM == 0) {
+        if (L.pm) {       // position-major rows + tap skipping (plan_taps vouches for mode 1 .. 3)
+            if (mode == 1) launch_igemm(conv3x3_igemm_kernel<BM, BN, WM, WN, 1, 0, true>, L, a);
+            else if (mode == 2) launch_igemm(conv3x3_igemm_kernel<BM, BN, WM, WN, 2, 0, true>, L, a);
+            else launch_igemm(conv3x3_igemm_kernel<BM, BN, WM, WN, 3, 0, true>, L, a);
+            return;
+        }
+    }
     if (mode == 1) launch_igemm(conv3x3_igemm_kernel<BM, BN, WM, WN, 1, GM>, L, a);
     else if (mode == 2) launch_igemm(conv3x3_igemm_kernel<BM, BN, WM, WN, 2, GM>, L, a);
     else if (mode == 3) launch_igemm(conv3x3_igemm_kernel<BM, BN, WM, WN, 3, GM>, L, a);
@@ -1693,8 +1920,6 @@ static int conv2d_fwd_impl(const float* x0, int ld0, int C0, const float* x1, in
         const double alg = phases == 4 ? 2.0 * 4.0 * (double)a.M * Cout * 9.0 * (C0 + C1)
                                        : (stride == 2 ? 2.0 * 4.0 * (double)a.M * Cout * 9.0 * (C0 + C1)
                                                       : 2.0 * (double)a.M * Cout * (double)ntaps * (C0 + C1));
-        // what the launch issues: the sub-pixel forms run 4 (forward) / 16 at a quarter of the pixels (data gradient) taps
-        ProfScope prof(K_CONV_FWD, s, alg, 2.0 * (double)a.M * phases * Cout * (double)ntaps * (C0 + C1));
         // loader: the 3x3 / pad 1 fast form when the caller vouches for clean pad channels and a block's pixel span
         // fits the 2^30-byte buffer window (always, short of ~2 M-float pixel rows)
         const long span = ((long)BK * 8 + 3L * (ups ? Wi / 2 : Wi) + 8) * (ld0 > ld1 ? ld0 : ld1) * 4;
@@ -1710,13 +1935,23 @@ static int conv2d_fwd_impl(const float* x0, int ld0, int C0, const float* x1, in
         if (mode == 0 && g_fast_loader && g_kxk_fast && a.clean && !ups && ntaps <= 32 && pad >= 0 && pad < kh && pad < kw &&
             span_k < (1L << 29) && (size_t)x0 % 16 == 0 && (!x1 || (size_t)x1 % 16 == 0))
             mode = 3;
+        // position-major rows where that lets blocks skip the K steps of taps that only read padding (plan_taps)
+        const TapGeom tg = {p.bm, N, Ho, Wo, Hi, Wi, kh, kw, pad, stride, phases};
+        const long src_pixels = (long)N * (ups ? Hi / 2 : Hi) * (ups ? Wi / 2 : Wi);
+        double row_taps;
+        const bool pm = plan_taps(p, mode, stats_partial && p.splits == 1, tg, src_pixels * (ld0 > ld1 ? ld0 : ld1) * 4, &row_taps);
+        fast_div_consts((unsigned)N, &a.mulF, &a.shF);
+        fast_div_consts((unsigned)kw, &a.mulKW, &a.shKW);
+        // what the launch issues: the sub-pixel forms run 4 (forward) / 16 at a quarter of the pixels (data gradient) taps; a
+        // position-major launch only the (row, tap) pairs of the taps its tiles do not skip
+        ProfScope prof(K_CONV_FWD, s, alg, 2.0 * row_taps * Cout * (double)(C0 + C1));
         // the roofline kernel is timed by its own begin / end stamps (bench.py `roofline`, agrees with rocprofv3)
         hipEvent_t ev0, ev1;
         const bool timed = prof.kernel_events(&ev0, &ev1);
         // (padding a block's LDS request so that exactly ceil(blocks / CUs) blocks fit a CU was built and measured in round 4: the
         // dispatcher already puts 1024 blocks on 256 CUs four by four -- tools/microbench/launch_gap.hip (e) -- and the step did
         // not move, 10.33 vs 10.32 ms: removed.  profiles/r04_knob_ab_log.txt)
-        const IgemmLaunch L = {grid, s, timed, ev0, ev1};
+        const IgemmLaunch L = {grid, s, timed, ev0, ev1, pm};
         if (p.bn == 16 || p.bn == 48 ? g_gemm16_bf16x3 : g_gemm_bf16x3) launch_plan_tile<1>(p, mode, L, a);
         else launch_plan_tile<0>(p, mode, L, a);
     }

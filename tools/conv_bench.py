@@ -29,6 +29,64 @@ def timeit(fn, iters):
 STATS = bool(int(os.environ.get('CB_STATS', '0')))
 
 
+def discriminator_rows(cfg, args, dev):
+    """the patch discriminator's four 4x4 / pad 0 convolutions (modules/discriminator.py) on the batched [generated | real]
+    pass: forward and data gradient (a pad-3 correlation over dy) with the executed rate next to the algorithmic one -- the
+    data gradients skip the K steps of taps that only read padding (tuning value ktap_skip; not part of the totals below)"""
+    import ctypes
+    dp, cp = cfg["model_params"]["discriminator_params"], cfg["model_params"]["common_params"]
+    frames = 2 * args.batch
+    from modules.discriminator import Discriminator
+    blocks = [(b.in_features, b.out_features) for b in Discriminator(**dp, **cp).down_blocks]
+    lib = _lib.lib()
+
+    def executed(fn):
+        lib.cdll.mnk_prof_reset()
+        lib.cdll.mnk_prof_enable(1)
+        fn()
+        torch.cuda.synchronize()
+        lib.cdll.mnk_prof_enable(0)
+        v = ctypes.c_double()
+        lib.cdll.mnk_prof_query_executed(0, ctypes.byref(v))
+        lib.cdll.mnk_prof_reset()
+        return v.value
+
+    print("%-16s %5s %5s %4s %7s | %8s %8s  (alg. TFLOP/s, ms) | executed: %6s %6s" % (
+        "discriminator", "cin", "cout", "hi", "frames", "fwd", "dgrad", "fwd", "dgrad"))
+    hi = args.size // dp.get("scale_factor", 1)
+    for i, (c, cout) in enumerate(blocks):
+        ho = hi - 3
+        if ho < 1:
+            break
+        x = torch.randn(frames, hi, hi, ops.ceil4(c), device=dev)
+        x[..., c:] = 0
+        dy = torch.randn(frames, ho, ho, ops.ceil4(cout), device=dev)
+        dy[..., cout:] = 0
+        wt = torch.randn(cout, c, 1, 4, 4, device=dev) * 0.05
+        wp = torch.empty(ops._query("mnk_conv2d_packed_floats", cout, c, 0, 16), device=dev)
+        wd = torch.empty(ops._query("mnk_conv2d_packed_floats", c, cout, 0, 16), device=dev)
+        ops._call("mnk_conv2d_pack_all", x, wt.data_ptr(), wp.data_ptr(), wd.data_ptr(), None, cout, c, 0, 16)
+        y, dx = torch.empty_like(dy), torch.empty_like(x)
+        nwf = ops._query("mnk_conv2d_workspace_floats", frames, ho, ho, c, 0, cout, 16)
+        nwd = ops._query("mnk_conv2d_workspace_floats", frames, hi, hi, cout, 0, c, 16)
+        ws = torch.empty(max(nwf, nwd, 1), device=dev)
+
+        def fwd():
+            ops._call("mnk_conv2d_fwd", x, x.data_ptr(), x.shape[-1], c, None, 0, 0, 2, hi, hi, 4, 4, 0, wp.data_ptr(), None, None, 0,
+                      y.data_ptr(), y.shape[-1], frames, ho, ho, cout, ws.data_ptr(), nwf, None)
+
+        def dgrad():
+            ops._call("mnk_conv2d_fwd", dy, dy.data_ptr(), dy.shape[-1], cout, None, 0, 0, 2, ho, ho, 4, 4, 3, wd.data_ptr(), None, None,
+                      0, dx.data_ptr(), dx.shape[-1], frames, hi, hi, c, ws.data_ptr(), nwd, None)
+
+        fl = 2.0 * 16 * c * cout * ho * ho * frames
+        t_f, t_d = timeit(fwd, args.iters), timeit(dgrad, args.iters)
+        print("%-16s %5d %5d %4d %7d | %5.1f %5.3f  %5.1f %5.3f | %15.1f %6.1f" % (
+            "disc.block%d" % i, c, cout, hi, frames, fl / t_f / 1e12, t_f * 1e3, fl / t_d / 1e12, t_d * 1e3,
+            executed(fwd) / t_f / 1e12, executed(dgrad) / t_d / 1e12))
+        hi = ho // 2
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="taichi")
@@ -92,6 +150,7 @@ def main():
             tot[kk][0] += fl
             tot[kk][1] += t
             tot[kk][2] += ex
+    discriminator_rows(cfg, args, dev)
     for kk, (fl, t, ex) in tot.items():
         print("TOTAL %-6s %.1f GFLOP in %.2f ms = %.1f TFLOP/s (%.1f%% of 157.3) algorithmic; executed %.1f GFLOP = %.1f TFLOP/s "
               "(%.1f%% of 157.3)" % (kk, fl / 1e9, t * 1e3, fl / t / 1e12, fl / t / 1e12 / 157.3 * 100, ex / 1e9, ex / t / 1e12,
