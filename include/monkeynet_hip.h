@@ -239,6 +239,14 @@ size_t mnk_conv3x3_stats_floats(int N, int H, int W, int C0, int C1, int Cout);
  * mnk_conv3x3_splits / mnk_conv3x3_up_splits of them -- and the caller sums them (mnk_bn_small_fwd does, together with the
  * normalisation that follows); y is not written */
 #define MNK_CONV_DEFER_SPLITK 4
+/* (= 8, forward only: mnk_conv3x3_fwd, mnk_conv3x3_up_fwd, mnk_conv2d_fwd) opt-in reduced-precision INFERENCE products.  The
+ * loaders round both operands -- activations and packed weights, fp32 in memory -- to bf16, round to nearest even; the products
+ * of the rounded operands are exact and are accumulated in fp32 on the bf16 matrix cores (one MFMA per tile and K step instead
+ * of the fp32 chain).  Everything else stays fp32: bias, residual, split-K partials and their reduction, deferred partials, the
+ * stores.  A property of the launch, not a tuning value: tile, split, workspace and the split queries are those of the same call
+ * without the flag.  Composes with the three flags above.  No backward kernel differentiates this form, so a non-NULL
+ * `stats_partial` (a training request) is rejected as an invalid argument and nothing is launched. */
+#define MNK_CONV_BF16 8
 int mnk_conv3x3_splits(int N, int H, int W, int C0, int C1, int Cout);
 int mnk_conv3x3_up_splits(int N, int H, int W, int C0, int C1, int Cout);
 int mnk_conv3x3_fwd(const float* x0, int ld0, int C0, const float* x1, int ld1, int C1, int flags, const float* wp,
@@ -267,7 +275,7 @@ size_t mnk_conv3x3_up_workspace_floats(int N, int H, int W, int C0, int C1, int 
 size_t mnk_conv3x3_up_stats_floats(int N, int H, int W, int C0, int C1, int Cout);
 int mnk_conv3x3_up_fwd(const float* x0, int ld0, int C0, const float* x1, int ld1, int C1, int flags, const float* wp_up,
                        const float* bias, float* y, int ld_y, int N, int H, int W, int Cout, float* ws, size_t ws_floats,
-                       float* stats_partial, void* stream);     /* flags: 0 or MNK_CONV_DEFER_SPLITK */
+                       float* stats_partial, void* stream);     /* flags: 0, MNK_CONV_DEFER_SPLITK and / or MNK_CONV_BF16 */
 size_t mnk_conv3x3_up_dgrad_workspace_floats(int N, int H, int W, int Cout, int C);
 int mnk_conv3x3_up_dgrad(const float* dy, int ld_dy, int Cout, const float* wp_up_dgrad, float* dx, int ld_dx, int N, int H,
                          int W, int C, float* ws, size_t ws_floats, void* stream);

@@ -491,7 +491,9 @@ __device__ unsigned long long mnk_phase_sclk[2 * 16384];      // the shader cloc
 constexpr int LDS_H = 24;     // padded LDS row of the bf16 planes (16 + 8 halves = 48 bytes: conflict-free b128 fragment reads)
 
 // GM: 0 -- v_mfma_f32_32x32x2_f32 on fp32 tiles; 1 -- the same products on the bf16 matrix cores: the loaders split every fp32
-// operand into three bf16 planes on its way to LDS and a K step of 16 is six v_mfma_f32_32x32x16_bf16 per tile (mnk_common.h)
+// operand into three bf16 planes on its way to LDS and a K step of 16 is six v_mfma_f32_32x32x16_bf16 per tile (mnk_common.h);
+// 2 -- the one-pass form (MNK_CONV_BF16): the loaders round every fp32 operand to ONE bf16 plane (nearest even) and a K step is
+// one v_mfma_f32_32x32x16_bf16 per tile; fp32 accumulation, and everything behind the accumulator is the fp32 epilogue
 // PM: position-major rows + block-uniform tap skipping (row_pixel, TapCursor): fast loaders and fp32 products only, and only
 // launches whose epilogue leaves no per-block column sums -- those are fp32 sums over the rows of a tile, and another row
 // order would change their bits
@@ -509,16 +511,21 @@ __global__ void __launch_bounds__(256, MNK_IGEMM_OCC) conv3x3_igemm_kernel(ConvA
     constexpr int NACC = (TM * TN == 1) ? MNK_IGEMM_NACC : 1;
     // 8 (16) registers per stage; the 128x128 tile has none to spare, and the bf16x3 form measured 0.05 ms per iteration
     // faster with one stage (profiles/r06_knob_ab_log.txt, v16): its six MFMAs per K step already cover the load latency
-    constexpr int NST = (BM * BN <= 64 * 128 && GM == 0) ? MNK_IGEMM_NST : 1;
+    // (the one-pass form, GM = 2, takes the fp32 rule: its one MFMA per tile covers even less latency, and two stages spill at 128x128)
+    constexpr int NST = (BM * BN <= 64 * 128 && GM != 1) ? MNK_IGEMM_NST : 1;
     static_assert(WM * WN == 4, "4 waves per block");
     static_assert(NST == 1 || NST == 2, "one or two register stages");
-    // one LDS image, two views: fp32 rows [2][rows][LDS_K] (GM 0) / three bf16 planes [2][3][rows][LDS_H] (GM 1)
-    constexpr int A_BYTES = GM ? 2 * 3 * BM * LDS_H * 2 : 2 * BM * LDS_K * 4, B_BYTES = GM ? 2 * 3 * BN * LDS_H * 2 : 2 * BN * LDS_K * 4;
+    // one LDS image, three views: fp32 rows [2][rows][LDS_K] (GM 0) / three bf16 planes [2][3][rows][LDS_H] (GM 1) / one bf16
+    // plane [2][rows][LDS_H] (GM 2)
+    constexpr int NPL = GM == 2 ? 1 : 3;
+    constexpr int A_BYTES = GM ? 2 * NPL * BM * LDS_H * 2 : 2 * BM * LDS_K * 4, B_BYTES = GM ? 2 * NPL * BN * LDS_H * 2 : 2 * BN * LDS_K * 4;
     __shared__ __attribute__((aligned(16))) unsigned char smem_a[A_BYTES], smem_b[B_BYTES];
     float (*const As)[BM][LDS_K] = reinterpret_cast<float (*)[BM][LDS_K]>(smem_a);
     float (*const Bs)[BN][LDS_K] = reinterpret_cast<float (*)[BN][LDS_K]>(smem_b);
     unsigned short (*const Ah)[3][BM][LDS_H] = reinterpret_cast<unsigned short (*)[3][BM][LDS_H]>(smem_a);
     unsigned short (*const Bh)[3][BN][LDS_H] = reinterpret_cast<unsigned short (*)[3][BN][LDS_H]>(smem_b);
+    unsigned short (*const Ao)[BM][LDS_H] = reinterpret_cast<unsigned short (*)[BM][LDS_H]>(smem_a);
+    unsigned short (*const Bo)[BN][LDS_H] = reinterpret_cast<unsigned short (*)[BN][LDS_H]>(smem_b);
 
     const int t = threadIdx.x;
     const int lane = t & 63, wave = t >> 6;
@@ -586,6 +593,12 @@ __global__ void __launch_bounds__(256, MNK_IGEMM_OCC) conv3x3_igemm_kernel(ConvA
             for (int j = 0; j < RA; ++j) *reinterpret_cast<float4*>(&As[buf][lrow + 64 * j][lq * 4]) = L.template masked<ST>(j);
             if (BN >= 64 || lrow < BN) *reinterpret_cast<float4*>(&Bs[buf][lrow][lq * 4]) = ST == 0 ? rb0a : rb0b;
             if constexpr (RB > 1) *reinterpret_cast<float4*>(&Bs[buf][lrow + 64][lq * 4]) = ST == 0 ? rb1a : rb1b;
+        } else if constexpr (GM == 2) {
+#pragma unroll
+            for (int j = 0; j < RA; ++j)
+                *reinterpret_cast<uint2*>(&Ao[buf][lrow + 64 * j][lq * 4]) = mnk_round_bf16x4(L.template masked<ST>(j));
+            if (BN >= 64 || lrow < BN) *reinterpret_cast<uint2*>(&Bo[buf][lrow][lq * 4]) = mnk_round_bf16x4(ST == 0 ? rb0a : rb0b);
+            if constexpr (RB > 1) *reinterpret_cast<uint2*>(&Bo[buf][lrow + 64][lq * 4]) = mnk_round_bf16x4(ST == 0 ? rb1a : rb1b);
         } else {
             uint2 p0, p1, p2;
 #pragma unroll
@@ -624,6 +637,26 @@ __global__ void __launch_bounds__(256, MNK_IGEMM_OCC) conv3x3_igemm_kernel(ConvA
     const int a_row0 = wm * (BM / WM) + fi, b_row0 = wn * (BN / WN) + fi;
 
     auto mfma_step = [&](int buf) __attribute__((always_inline)) {
+        if constexpr (GM == 2) {
+            // lane (fi, fk) holds k = 8 fk .. 8 fk + 7 of its row: one b128 per operand row, one MFMA per tile
+            mnk_bf16x8 ha[TM], hb[TN];
+#pragma unroll
+            for (int i = 0; i < TM; ++i) ha[i] = mnk_as_bf16x8(*reinterpret_cast<const uint4*>(&Ao[buf][a_row0 + 32 * i][fk * 8]));
+#pragma unroll
+            for (int j = 0; j < TN; ++j) hb[j] = mnk_as_bf16x8(*reinterpret_cast<const uint4*>(&Bo[buf][b_row0 + 32 * j][fk * 8]));
+            if constexpr (NACC == 2) {
+                // a one-tile wave: even K steps (LDS buffer 0) feed one accumulator set, odd ones the other -- neighbours independent
+                if (buf) acc[1][0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ha[0], hb[0], acc[1][0][0], 0, 0, 0);
+                else acc[0][0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ha[0], hb[0], acc[0][0][0], 0, 0, 0);
+            } else {
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j)
+                        acc[0][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ha[i], hb[j], acc[0][i][j], 0, 0, 0);
+            }
+            return;
+        }
         if constexpr (GM == 1) {
             // lane (fi, fk) holds k = 8 fk .. 8 fk + 7 of its row in every plane: one b128 per plane and operand row
             mnk_bf16x8 ha[3][TM], hb[3][TN];
@@ -883,16 +916,20 @@ __global__ void __launch_bounds__(256, MNK_IGEMM_OCC) conv3x3_igemm_kernel(ConvA
 // the loop works on PAIRS of steps -- step 2p lands in LDS buffer 0, step 2p + 1 in buffer 1 (zeros behind an odd count), lane
 // (fi, fk) reads k = 8 fk .. 8 fk + 7 of its row from buffer fk >> 1 -- six MFMAs per 16x16 tile and pair.  Two register stages
 // hold the next pair while the MFMAs of this one run; two barriers per pair.
+// GM = 2: the one-pass form (MNK_CONV_BF16) -- the same pairs with ONE rounded plane per operand and one MFMA per tile and pair.
 template <int BN, int MODE, int GM = 0>
 __global__ void __launch_bounds__(256) conv3x3_igemm16_kernel(ConvArgs a) {
     constexpr int BM = 128, RA = 2, TM = 2, TN = BN / 16;
     constexpr int NSTG = GM ? 2 : 1;
-    constexpr int A_BYTES = GM ? 2 * 3 * BM * LDS_H * 2 : 2 * BM * LDS_K * 4, B_BYTES = GM ? 2 * 3 * BN * LDS_H * 2 : 2 * BN * LDS_K * 4;
+    constexpr int NPL = GM == 2 ? 1 : 3;      // bf16 planes per operand
+    constexpr int A_BYTES = GM ? 2 * NPL * BM * LDS_H * 2 : 2 * BM * LDS_K * 4, B_BYTES = GM ? 2 * NPL * BN * LDS_H * 2 : 2 * BN * LDS_K * 4;
     __shared__ __attribute__((aligned(16))) unsigned char smem_a[A_BYTES], smem_b[B_BYTES];
     float (*const As)[BM][LDS_K] = reinterpret_cast<float (*)[BM][LDS_K]>(smem_a);
     float (*const Bs)[BN][LDS_K] = reinterpret_cast<float (*)[BN][LDS_K]>(smem_b);
     unsigned short (*const Ah)[3][BM][LDS_H] = reinterpret_cast<unsigned short (*)[3][BM][LDS_H]>(smem_a);
     unsigned short (*const Bh)[3][BN][LDS_H] = reinterpret_cast<unsigned short (*)[3][BN][LDS_H]>(smem_b);
+    unsigned short (*const Ao)[BM][LDS_H] = reinterpret_cast<unsigned short (*)[BM][LDS_H]>(smem_a);
+    unsigned short (*const Bo)[BN][LDS_H] = reinterpret_cast<unsigned short (*)[BN][LDS_H]>(smem_b);
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     int bx, by;
     xcd_tile(a.xcd, bx, by);
@@ -928,7 +965,7 @@ __global__ void __launch_bounds__(256) conv3x3_igemm16_kernel(ConvArgs a) {
             for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
 
     const int fi = lane & 15, fk = lane >> 4;     // row/col inside a 16-tile, k group 0..3
-    if constexpr (GM == 1) {
+    if constexpr (GM != 0) {
         using S0 = std::integral_constant<int, 0>;
         using S1 = std::integral_constant<int, 1>;
         // loads of K step s into register stage ST (the activation loader keeps its own cursor: steps in order)
@@ -942,6 +979,13 @@ __global__ void __launch_bounds__(256) conv3x3_igemm16_kernel(ConvArgs a) {
         auto store_h = [&](auto st_tag, bool zero) __attribute__((always_inline)) {
             constexpr int ST = decltype(st_tag)::value;
             const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (GM == 2) {
+#pragma unroll
+                for (int j = 0; j < RA; ++j)
+                    *reinterpret_cast<uint2*>(&Ao[ST][lrow + 64 * j][lq * 4]) = mnk_round_bf16x4(zero ? z : L.template masked<ST>(j));
+                if (lrow < BN) *reinterpret_cast<uint2*>(&Bo[ST][lrow][lq * 4]) = mnk_round_bf16x4(zero ? z : (ST == 0 ? rb : rb1));
+                return;
+            }
             uint2 p0, p1, p2;
 #pragma unroll
             for (int j = 0; j < RA; ++j) {
@@ -959,6 +1003,18 @@ __global__ void __launch_bounds__(256) conv3x3_igemm16_kernel(ConvArgs a) {
         };
         const int kb = fk >> 1, ko = (fk & 1) * 8;      // this lane's k group: LDS buffer and offset inside the step
         auto mfma_pair = [&]() __attribute__((always_inline)) {
+            if constexpr (GM == 2) {
+                mnk_bf16x8 oa[TM], ob[TN];
+#pragma unroll
+                for (int i = 0; i < TM; ++i) oa[i] = mnk_as_bf16x8(*reinterpret_cast<const uint4*>(&Ao[kb][wave * 32 + 16 * i + fi][ko]));
+#pragma unroll
+                for (int j = 0; j < TN; ++j) ob[j] = mnk_as_bf16x8(*reinterpret_cast<const uint4*>(&Bo[kb][16 * j + fi][ko]));
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(oa[i], ob[j], acc[i][j], 0, 0, 0);
+                return;
+            }
             mnk_bf16x8 ha[3][TM], hb[3][TN];
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) {
@@ -1688,14 +1744,15 @@ static double issued_row_taps(const TapGeom& g) {
     return total;
 }
 
-// Does this launch run position-major?  Only the 32x32-tile fp32 kernels through a buffer-load loader have the form; the
+// Does this launch run position-major?  Only the 32x32-tile fp32 kernels through a buffer-load loader have the form (not the
+// bf16x3 kernels, not a one-pass MNK_CONV_BF16 launch); the
 // sources must fit the loaders' window from the start of the tensor (the rows of a tile lie a frame apart); an unsplit launch
 // with a column-sum epilogue keeps the frame-major order (its sums are sums over a tile's rows; a split launch's sums come
 // from the reduction, which walks memory order); and the order must pay: ktap_skip_min.  *row_taps: the pairs it issues.
-static bool plan_taps(const Plan& p, int mode, bool column_sums, const TapGeom& g, long src_bytes, double* row_taps) {
+static bool plan_taps(const Plan& p, int mode, bool one_pass, bool column_sums, const TapGeom& g, long src_bytes, double* row_taps) {
     const double all = (double)g.N * g.H * g.W * g.phases * g.kh * g.kw;
     *row_taps = all;
-    if (!g_ktap_skip || g_gemm_bf16x3 || p.bn == 16 || p.bn == 48 || mode < 1 || mode > 3) return false;
+    if (!g_ktap_skip || g_gemm_bf16x3 || one_pass || p.bn == 16 || p.bn == 48 || mode < 1 || mode > 3) return false;
     if (column_sums || src_bytes >= (1L << 29) || g.kh * g.kw > 32) return false;
     // no tile order can skip more than the (position, tap) pairs that are outside: a product of two one-dimensional counts
     double inside = 0.0;
@@ -1798,7 +1855,7 @@ static void launch_igemm(void (*kernel)(ConvArgs), const IgemmLaunch& L, const C
     if (L.timed) hipExtLaunchKernelGGL(kernel, L.grid, dim3(256), 0, L.s, L.ev0, L.ev1, 0, a);
     else hipLaunchKernelGGL(kernel, L.grid, dim3(256), 0, L.s, a);
 }
-// the 32x32-MFMA kernel of a tile / the 16x16-MFMA kernel of a width, by loader mode; GM: 1 = bf16x3 products
+// the 32x32-MFMA kernel of a tile / the 16x16-MFMA kernel of a width, by loader mode; GM: 1 = bf16x3 products, 2 = one-pass bf16
 template <int BM, int BN, int WM, int WN, int GM>
 static void launch_tile(int mode, const IgemmLaunch& L, const ConvArgs& a) {
     if constexpr (GM == 0) {
@@ -1840,8 +1897,12 @@ static int conv2d_fwd_impl(const float* x0, int ld0, int C0, const float* x1, in
                            int kw, int pad, int stride, int phases, const float* wp, const float* bias, const float* residual,
                            int ld_res, float* y, int ld_y, int N, int Ho, int Wo, int Cout, float* ws, size_t ws_floats,
                            float* stats_partial, void* stream, const BnBwdSrc* bnb = nullptr) {
-    MNK_REQUIRE(flags >= 0 && flags <= 7);
+    MNK_REQUIRE(flags >= 0 && flags <= 15);
     const int ups = flags & MNK_CONV_UPSAMPLED, clean = (flags & MNK_CONV_CLEAN_PADS) ? 1 : 0;
+    // MNK_CONV_BF16: the one-pass bf16 products (GM = 2) -- a property of this launch; tile and split are those of the fp32 plan.
+    // Inference only: the column sums of the epilogue are a training request, and no backward kernel differentiates this form
+    const bool one_pass = (flags & MNK_CONV_BF16) != 0;
+    MNK_REQUIRE(!one_pass || (!stats_partial && !bnb));
     // MNK_CONV_DEFER_SPLITK: a split-K launch leaves its partials in `ws` ([split][phase][M][ldw], bias not added) and the
     // caller sums them (mnk_bn_small_fwd does, together with the normalisation that follows)
     const bool defer_splitk = (flags & MNK_CONV_DEFER_SPLITK) != 0;
@@ -1939,7 +2000,7 @@ static int conv2d_fwd_impl(const float* x0, int ld0, int C0, const float* x1, in
         const TapGeom tg = {p.bm, N, Ho, Wo, Hi, Wi, kh, kw, pad, stride, phases};
         const long src_pixels = (long)N * (ups ? Hi / 2 : Hi) * (ups ? Wi / 2 : Wi);
         double row_taps;
-        const bool pm = plan_taps(p, mode, stats_partial && p.splits == 1, tg, src_pixels * (ld0 > ld1 ? ld0 : ld1) * 4, &row_taps);
+        const bool pm = plan_taps(p, mode, one_pass, stats_partial && p.splits == 1, tg, src_pixels * (ld0 > ld1 ? ld0 : ld1) * 4, &row_taps);
         fast_div_consts((unsigned)N, &a.mulF, &a.shF);
         fast_div_consts((unsigned)kw, &a.mulKW, &a.shKW);
         // what the launch issues: the sub-pixel forms run 4 (forward) / 16 at a quarter of the pixels (data gradient) taps; a
@@ -1952,7 +2013,8 @@ static int conv2d_fwd_impl(const float* x0, int ld0, int C0, const float* x1, in
         // dispatcher already puts 1024 blocks on 256 CUs four by four -- tools/microbench/launch_gap.hip (e) -- and the step did
         // not move, 10.33 vs 10.32 ms: removed.  profiles/r04_knob_ab_log.txt)
         const IgemmLaunch L = {grid, s, timed, ev0, ev1, pm};
-        if (p.bn == 16 || p.bn == 48 ? g_gemm16_bf16x3 : g_gemm_bf16x3) launch_plan_tile<1>(p, mode, L, a);
+        if (one_pass) launch_plan_tile<2>(p, mode, L, a);
+        else if (p.bn == 16 || p.bn == 48 ? g_gemm16_bf16x3 : g_gemm_bf16x3) launch_plan_tile<1>(p, mode, L, a);
         else launch_plan_tile<0>(p, mode, L, a);
     }
     if (p.splits > 1 && !defer_splitk) {
@@ -2032,7 +2094,7 @@ size_t mnk_conv3x3_up_stats_floats(int N, int H, int W, int C0, int C1, int Cout
 int mnk_conv3x3_up_fwd(const float* x0, int ld0, int C0, const float* x1, int ld1, int C1, int flags, const float* wp_up,
                        const float* bias, float* y, int ld_y, int N, int H, int W, int Cout, float* ws, size_t ws_floats,
                        float* stats_partial, void* stream) {
-    MNK_REQUIRE((flags & ~MNK_CONV_DEFER_SPLITK) == 0);
+    MNK_REQUIRE((flags & ~(MNK_CONV_DEFER_SPLITK | MNK_CONV_BF16)) == 0);
     return conv2d_fwd_impl(x0, ld0, C0, x1, ld1, C1, MNK_CONV_CLEAN_PADS | flags, H, W, 2, 2, 1, 1, 4, wp_up, bias, nullptr, 0, y,
                            ld_y, N, H, W, Cout, ws, ws_floats, stats_partial, stream);
 }

@@ -40,6 +40,10 @@
 // product -- measured: the same error against fp64 as the fp32 MFMA chain (tools/microbench/bf16x3_gemm.hip,
 // tests/test_kernels_conv.py) -- at 2.67 x the matrix rate.  The split is made by the loaders between the global load and the LDS
 // store with the hardware conversion (v_cvt_pk_bf16_f32, round to nearest even): 4.5 vector instructions per element.
+//
+// One-pass bf16 products (MNK_CONV_BF16, opt-in inference): keeping only the first plane (x1 = bf16(x), round to nearest even) is
+// a REDUCED-precision product -- both operands carry 8 mantissa bits, every product of two of them is exact in fp32 and the
+// matrix core accumulates in fp32: one conversion per element, one plane in LDS, one MFMA per tile and K step (mnk_round_bf16x4).
 #ifdef HIPEMU
 typedef unsigned short mnk_bf16x8 __attribute__((vector_size(16)));
 static inline unsigned mnk_bf16_rn_bits(float x) {       // round to nearest even, NaN stays NaN (what v_cvt_pk_bf16_f32 does)
@@ -74,6 +78,11 @@ static inline mnk_bf16x8 mnk_as_bf16x8(uint4 v) {
     memcpy(&r, &v, 16);
     return r;
 }
+// float4 -> four bf16, round to nearest even: the one-pass form's only plane (the first plane of mnk_split3)
+static inline uint2 mnk_round_bf16x4(float4 v) {
+    const unsigned h0 = mnk_bf16_rn_bits(v.x), h1 = mnk_bf16_rn_bits(v.y), h2 = mnk_bf16_rn_bits(v.z), h3 = mnk_bf16_rn_bits(v.w);
+    return make_uint2(h0 | (h1 << 16), h2 | (h3 << 16));
+}
 #else
 typedef __attribute__((ext_vector_type(8))) __bf16 mnk_bf16x8;
 typedef __attribute__((ext_vector_type(2))) __bf16 mnk_bf16x2;
@@ -92,6 +101,12 @@ __device__ __forceinline__ void mnk_split3(float4 v, uint2& p0, uint2& p1, uint2
     p2 = make_uint2(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b));
 }
 __device__ __forceinline__ mnk_bf16x8 mnk_as_bf16x8(uint4 v) { return __builtin_bit_cast(mnk_bf16x8, v); }
+// float4 -> four bf16 with the hardware conversion (round to nearest even): the one-pass form's only plane
+__device__ __forceinline__ uint2 mnk_round_bf16x4(float4 v) {
+    const mnk_f32x2 lo = {v.x, v.y}, hi = {v.z, v.w};
+    const mnk_bf16x2 a = __builtin_convertvector(lo, mnk_bf16x2), b = __builtin_convertvector(hi, mnk_bf16x2);
+    return make_uint2(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b));
+}
 #endif
 
 namespace mnk {

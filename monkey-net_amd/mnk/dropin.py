@@ -453,7 +453,10 @@ class EvalRunner:
     the evaluation-mode norm coefficients are made before the capture and only referenced by it (a captured forward of
     mnk.engine.Reconstructor re-packs inside the graph: right for a batch of 512, most of the launches at batch 1) -- and replayed
     per call: inputs are copied into static buffers, outputs are returned as fresh tensors (the loop keeps `kp_source` across
-    calls).  Re-captured when a parameter, a buffer or the optimiser epoch changed (load_state_dict between two videos)."""
+    calls).  Re-captured when a parameter, a buffer or the optimiser epoch changed (load_state_dict between two videos).
+    The forward is captured inside ops.inference_precision(eval_precision()) -- an enclosing bf16 scope, else MNK_EVAL_PRECISION;
+    the precision is part of the program key, so a changed scope or variable captures a program of its own instead of replaying
+    the other form."""
 
     MAX_PROGRAMS = 8
 
@@ -494,12 +497,14 @@ class EvalRunner:
         key = self._flatten((inputs, kwargs), flat)
         if not flat or any(t.dtype != torch.float32 for _, t in flat):
             return NotImplemented
+        precision = eval_precision()
+        key = (precision, key)
         fp = self._fingerprint(module)
         prog = self.programs.get(key)
         if prog is None or prog["fp"] != fp:
             if len(self.programs) >= self.MAX_PROGRAMS:
                 self.programs.clear()
-            prog = self.programs[key] = self._capture(module, inputs, kwargs, flat, device, fp)
+            prog = self.programs[key] = self._capture(module, inputs, kwargs, flat, device, fp, precision)
         dsts, srcs = [], []
         for i, ((path, t), s) in enumerate(zip(flat, prog["static"])):
             if t.device.type == "cpu" and not t.is_pinned():
@@ -537,21 +542,21 @@ class EvalRunner:
         ring["buf"][k].copy_(t)
         return ring["buf"][k], ring["ev"][k]
 
-    def _capture(self, module, inputs, kwargs, flat, device, fp):
+    def _capture(self, module, inputs, kwargs, flat, device, fp, precision="fp32"):
         static = [t.to(device).clone() for _, t in flat]
         leaves = {path: s for (path, _), s in zip(flat, static)}
         s_in, s_kw = self._rebuild((inputs, kwargs), leaves)
         cap = torch.cuda.Stream()
         cap.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(cap):         # the caches are keyed by stream: fill them on the stream the capture runs on
-            for _ in range(2):
+        with torch.cuda.stream(cap), mops.inference_precision(precision):     # the caches are keyed by stream: fill them on the
+            for _ in range(2):                                               # stream the capture runs on
                 module(*s_in, **s_kw)
         torch.cuda.current_stream().wait_stream(cap)
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
         mops.FROZEN_CAPTURE[0] = True
         try:
-            with torch.cuda.graph(graph, stream=cap):
+            with torch.cuda.graph(graph, stream=cap), mops.inference_precision(precision):
                 out = module(*s_in, **s_kw)
         finally:
             mops.FROZEN_CAPTURE[0] = False
@@ -578,6 +583,14 @@ def _walk_clone(obj):
     if isinstance(obj, (list, tuple)):
         return type(obj)(_walk_clone(v) for v in obj)
     return obj
+
+
+def eval_precision():
+    """the precision of an evaluation-mode forward behind DataParallelWithCallback: the enclosing ops.inference_precision scope
+    where it is not fp32 (a wrapper handed to Reconstructor(precision="bf16") or called inside the scope), else MNK_EVAL_PRECISION.
+    The captured program and the eager fall-backs (MNK_EVAL_GRAPH=0, a signature the runner declines) both use it."""
+    scope = mops.current_precision()
+    return scope if scope != "fp32" else mops.check_precision(knobs.get("MNK_EVAL_PRECISION"))
 
 
 def eval_runner_for(wrapper):

@@ -554,10 +554,13 @@ class Reconstructor:
     mode BatchNorm uses running statistics, so frames are independent and (video, frame) folds into the batch.  With
     use_graph the whole forward (kp detector x2 + generator, ~250 launches + the weight packs) is captured once as a
     hipGraph and replayed per batch (BASELINE config 5: "hipGraph-captured generator forward").  The returned tensors of
-    the graph form are static buffers that the next call overwrites: clone what must survive."""
+    the graph form are static buffers that the next call overwrites: clone what must survive.
+    precision: "fp32", or "bf16" -- the forward runs inside ops.inference_precision(precision): the 3x3 convolutions round their
+    operands to bf16 ("bf16 inference").  A captured graph keeps the precision it was built with."""
 
-    def __init__(self, kp_detector, generator, use_graph=False):
+    def __init__(self, kp_detector, generator, use_graph=False, precision="fp32"):
         self.kp_detector, self.generator = kp_detector.eval(), generator.eval()
+        self.precision = mops.check_precision(precision)
         self.use_graph = bool(use_graph)
         self._graph = None
         self._static_in = None
@@ -565,9 +568,10 @@ class Reconstructor:
 
     @torch.no_grad()
     def _forward(self, source, driving):
-        kp_source = self.kp_detector(source)
-        kp_driving = self.kp_detector(driving)
-        out = self.generator(source, kp_driving=kp_driving, kp_source=kp_source)
+        with mops.inference_precision(self.precision):
+            kp_source = self.kp_detector(source)
+            kp_driving = self.kp_detector(driving)
+            out = self.generator(source, kp_driving=kp_driving, kp_source=kp_source)
         return {"video_prediction": out["video_prediction"], "video_deformed": out["video_deformed"],
                 "kp_driving_mean": kp_driving["mean"], "kp_source_mean": kp_source["mean"]}
 
@@ -636,15 +640,20 @@ class Transfer:
     (video, frame) pairs folded into the batch.  Eval mode (running BatchNorm statistics), so frames are independent.
     Returns the dict transfer_one returns.  shared_source=True hands the generator the B source images and the (B, d)
     key points as they are: the appearance encoder runs once per source instead of once per frame, and its skip tensors
-    exist once (B instead of B*d rows); False repeats the source d times along the batch axis."""
+    exist once (B instead of B*d rows); False repeats the source d times along the batch axis.
+    precision: "fp32" or "bf16", the ops.inference_precision scope the call runs in (see Reconstructor)."""
 
-    def __init__(self, kp_detector, generator, normalization_params, shared_source=False):
+    def __init__(self, kp_detector, generator, normalization_params, shared_source=False, precision="fp32"):
         self.kp_detector, self.generator = kp_detector.eval(), generator.eval()
+        self.precision = mops.check_precision(precision)
         self.params = dict(normalization_params)
         self.shared_source = bool(shared_source)
 
-    @torch.no_grad()
     def __call__(self, source_image, driving_video):
+        with torch.no_grad(), mops.inference_precision(self.precision):
+            return self._run(source_image, driving_video)
+
+    def _run(self, source_image, driving_video):
         b, c, d, h, w = driving_video.shape
         kp_driving = self.kp_detector(driving_video)                     # (B, d, K, .)
         kp_source = self.kp_detector(source_image)                       # (B, 1, K, .)

@@ -34,6 +34,11 @@ KNOBS = {
     "MNK_EVAL_GRAPH": ("1", "DataParallelWithCallback around a KPDetector / MotionTransferGenerator in evaluation mode under no_grad "
                             "(reconstruction.py:45-62's per-frame loop): the forward is captured once per input signature as a "
                             "hipGraph with frozen weights and replayed (mnk.dropin.EvalRunner); 0: eager launches"),
+    "MNK_EVAL_PRECISION": ("fp32", "the evaluation-mode forward that mnk.dropin.EvalRunner captures for the reference's own per-frame "
+                                   "loops: fp32, or bf16 = the 3x3 convolutions round their operands to bf16 "
+                                   "(mnk.ops.inference_precision; INTEGRATION.md).  Part of the captured program's key: changing the "
+                                   "variable re-captures instead of replaying the other form.  An enclosing bf16 "
+                                   "inference_precision scope takes precedence; the wrapper's eager fall-backs use the same value"),
     "MNK_ADOPT_ADAM": ("1", "a stock torch.optim.Adam over a network whose gradients the drop-in runner keeps in one flat buffer is "
                             "stepped by mnk_adam_multi on the optimiser's own state tensors (mnk.optim.AdoptedAdam); 0: the stock step"),
     "MNK_NATIVE_PREDICTION": ("0", "1: `import modules.prediction_module` (prediction.py:10) resolves to mnk.predictor, the key-point "

@@ -617,6 +617,54 @@ def _gemm_launch(form, x0, c0, x1, c1, wp, bias, residual, n, h, w, cout, flags=
     return y, st
 
 
+# ---- opt-in bf16 inference ------------------------------------------------------------------------------------------------------
+# the precision of the 3x3 / sub-pixel forward GEMMs launched under torch.no_grad(): "fp32", or "bf16" = MNK_CONV_BF16 (operands
+# rounded to nearest-even bf16 in the loaders, exact products, fp32 accumulation; include/monkeynet_hip.h).  Everything else --
+# 1x1, grouped 1x1, embedding, warp, soft-argmax, norm layers -- is memory-bound and stays fp32.
+PRECISIONS = ("fp32", "bf16")
+
+
+def bf16_excluded(cin, cout):
+    """layers that keep the fp32 form inside inference_precision("bf16"): the 16-wide tile of conv3x3_igemm16_kernel (Cout <= 16) fed
+    by 64 or more input channels -- the dense-motion mask head, 76 or 98 -> 13.  Measured (profiles/bf16_inference.txt, section 3a)
+    the one-pass form gains 1.02 ... 1.17 x there and missed the per-layer gate on bair batch 512 (2M rows: 0.735 -> 0.718 ms,
+    spread 0.021).  The narrower key-point heat-map head (35 -> 10; 1.16 ... 1.24 x, outside the gate's range) keeps the flag."""
+    return cout <= 16 and cin >= 64
+
+_PRECISION = ["fp32"]
+
+
+def check_precision(precision):
+    if precision not in PRECISIONS:
+        raise ValueError("precision must be one of %s, not %r" % (PRECISIONS, precision))
+    return precision
+
+
+class inference_precision:
+    """Context manager: inside `with inference_precision("bf16"):` every 3x3 and sub-pixel forward convolution launched under
+    torch.no_grad() runs its products in one bf16 pass.  A convolution called with gradients enabled inside the scope raises
+    RuntimeError: the backward kernels are fp32 and would not differentiate what was computed.  Outside any scope the precision
+    is fp32; the previous value is restored on exit, also after an exception.
+    The precision is one value per process, not per thread: a scope opened in one thread also changes the convolutions another
+    thread launches meanwhile.  The loops here are single-threaded; keep an fp32 forward of another thread out of the scope."""
+
+    def __init__(self, precision):
+        self.precision = check_precision(precision)
+
+    def __enter__(self):
+        self.previous = _PRECISION[0]
+        _PRECISION[0] = self.precision
+        return self
+
+    def __exit__(self, *exc):
+        _PRECISION[0] = self.previous
+        return False
+
+
+def current_precision():
+    return _PRECISION[0]
+
+
 def _conv_launch(x0, c0, x1, c1, ups, wp, bias, residual, n, h, w, cout, want_stats=False, up=False, eval_defer=False):
     """One conv launch.  With want_stats the BatchNorm sums of the output come out of the conv epilogue (finished by a
     tiny second-stage kernel) instead of a separate pass over y; returns (y, sums or None).  up: `wp` holds the
@@ -632,6 +680,9 @@ def _conv_launch(x0, c0, x1, c1, ups, wp, bias, residual, n, h, w, cout, want_st
     # flags: bit 0 = nearest x2 up-sampled view, bit 1 = MNK_CONV_CLEAN_PADS -- every act this module produces has zero
     # pad channels (tests/test_modules.py::test_pad_channels_are_written pins that), so the fast 3x3 loader applies
     form, hq, wq, flags = ("up", h // 2, w // 2, 0) if up else ("3x3", h, w, int(ups) | 2)
+    # MNK_CONV_BF16 (conv3x3 vouches for no_grad and an evaluation-mode norm layer).  Not for bf16_excluded layers: they stay fp32
+    if _PRECISION[0] == "bf16" and not bf16_excluded(c0 + c1, cout):
+        flags |= 8
     y, st = _gemm_launch(form, x0, c0, x1, c1, wp, bias, residual, n, hq, wq, cout, flags, want_stats and not small, small or evald)
     if small:
         return y, y.new_empty(0)
@@ -908,6 +959,13 @@ def conv3x3(x0, c0, weight, bias=None, x1=None, c1=0, ups=False, residual=None, 
     eval_bn: the caller vouches that y's ONLY consumer is the evaluation-mode norm layer it calls next (bn_act): under no_grad a
     split-K launch then leaves its partials to that layer (mnk_bn_eval_split_fwd: reduction + affine + ReLU + pool in one launch)
     and y is never written."""
+    if _PRECISION[0] != "fp32":
+        if torch.is_grad_enabled():
+            raise RuntimeError("a convolution with gradients enabled inside inference_precision(%r): the backward kernels are "
+                               "fp32 and would not differentiate what was computed -- call it under torch.no_grad()" % _PRECISION[0])
+        if want_stats:
+            raise RuntimeError("inference_precision(%r) is for evaluation-mode networks: a training-mode norm layer asked this "
+                               "convolution for batch statistics" % _PRECISION[0])
     track = torch.is_grad_enabled() and any(
         t is not None and t.requires_grad for t in (x0, x1, weight, bias, residual))
     eval_defer = bool(eval_bn and not want_stats and residual is None and not torch.is_grad_enabled()

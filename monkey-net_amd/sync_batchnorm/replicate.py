@@ -137,6 +137,13 @@ class DataParallelWithCallback(nn.Module):
                 out = runner(inputs, kwargs, dev)
                 if out is not NotImplemented:
                     return out
+            if not torch.is_grad_enabled():
+                # the eager fall-backs (MNK_EVAL_GRAPH=0, a signature the runner declines) in the precision the runner would have
+                # captured in: MNK_EVAL_PRECISION, or the enclosing scope (with gradients enabled the variable does not apply)
+                from mnk import ops as mops
+                inputs, kwargs = self._scatter(inputs, kwargs, dev)
+                with mops.inference_precision(dropin.eval_precision()):
+                    return self.module(*_to_device(inputs, dev), **_to_device(kwargs, dev))
         inputs, kwargs = self._scatter(inputs, kwargs, dev)
         return self.module(*_to_device(inputs, dev), **_to_device(kwargs, dev))
 

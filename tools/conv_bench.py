@@ -1,6 +1,8 @@
 #!/usr/bin/env python
 """Per-layer micro-benchmark of the conv3x3 kernels (forward / dgrad / wgrad) on the layer shapes of one config.
-Usage on the GPU box:  python tools/conv_bench.py --config taichi --batch 32 [--size 64]"""
+Usage on the GPU box:  python tools/conv_bench.py --config taichi --batch 32 [--size 64]
+--onepass: the forward launches only, at an inference batch, fp32 against the one-pass bf16 form (MNK_CONV_BF16) -- the two forms
+alternate, `--reps` timings each, median and spread (max - min) per form; the exit status is 1 when a gated layer is not faster."""
 import argparse
 import os
 import sys
@@ -87,14 +89,72 @@ def discriminator_rows(cfg, args, dev):
         hi = ho // 2
 
 
+def onepass_rows(cfg, args, dev):
+    """every distinct 3x3 forward launch of mnk.engine.Reconstructor at batch `args.batch` (the key-point detector sees source
+    and driving frames in one call: 2 x batch frames; the generator sees batch): fp32 and one-pass bf16 timed alternately.
+    GATE rows: M >= 8192 pixel rows and Cin >= 64 -- the one-pass form must be faster by more than three times the larger of
+    the two spreads.  Layers ops._conv_launch keeps fp32 inside the scope (ops.bf16_excluded) are marked and not gated.
+    Returns the number of gated layers that are not faster."""
+    layers = workload.conv_flops_hot_path(cfg, args.size, args.size)["layers"]
+    print("one-pass bf16 against fp32, %s batch %d @ %d: median ms of %d x %d launches, (spread = max - min)" % (
+        args.config, args.batch, args.size, args.reps, args.iters))
+    print("%-16s %5s %5s %4s %8s | %9s %9s | %9s %9s | %6s  %s" % ("layer", "cin", "cout", "hw", "M", "fp32 ms", "spread", "bf16 ms",
+                                                                  "spread", "x", "gate (M >= 8192, cin >= 64)"))
+    seen, tot, failed = set(), [0.0, 0.0], 0
+    for name, cin, cout, h, w, k, flops in layers:
+        ups = ".dec" in name
+        frames = args.batch * (2 if name.startswith("kp") else 1)
+        key = (cin, cout, h, w, frames, ups)
+        if k != 3 or key in seen:
+            continue
+        seen.add(key)
+        hs, ws_ = (h // 2, w // 2) if ups else (h, w)
+        x = torch.randn(frames, hs, ws_, ops.ceil4(cin), device=dev)
+        x[..., cin:] = 0
+        wt = torch.randn(cout, cin, 1, 3, 3, device=dev) * 0.05
+        bias = torch.randn(cout, device=dev)
+        up = ops.subpixel(ups)
+        wp = ops._packed_fwd_weight(wt, cout, cin, 0, up)
+
+        def run(precision):
+            with ops.inference_precision(precision):
+                ops._conv_launch(x, cin, None, 0, ups, wp, bias, None, frames, h, w, cout, False, up)
+
+        times = {"fp32": [], "bf16": []}
+        for _ in range(args.reps):
+            for precision in ("fp32", "bf16"):
+                times[precision].append(timeit(lambda: run(precision), args.iters) * 1e3)
+        med = {p: sorted(v)[len(v) // 2] for p, v in times.items()}
+        spread = {p: max(v) - min(v) for p, v in times.items()}
+        m = frames * h * w
+        excluded = ops.bf16_excluded(cin, cout)       # ops._conv_launch keeps these heads fp32: both columns time the fp32 form
+        gated = m >= 8192 and cin >= 64 and not excluded
+        ok = med["fp32"] - med["bf16"] > 3.0 * max(spread.values())
+        failed += gated and not ok
+        tot[0] += med["fp32"]
+        tot[1] += med["bf16"]
+        print("%-16s %5d %5d %4d %8d | %9.4f %9.4f | %9.4f %9.4f | %6.2f  %s" % (
+            name, cin, cout, h, m, med["fp32"], spread["fp32"], med["bf16"], spread["bf16"], med["fp32"] / med["bf16"],
+            "excluded: fp32 in both columns" if excluded else ("PASS" if ok else "FAIL") if gated else ("-" if ok else "- (not faster)")))
+    print("TOTAL fwd fp32 %.3f ms, one-pass bf16 %.3f ms (%.2f x); gated layers that are not faster: %d" % (
+        tot[0], tot[1], tot[0] / tot[1], failed))
+    return failed
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="taichi")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--size", type=int, default=64)
     ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--onepass", action="store_true", help="forward only: fp32 against the one-pass bf16 form, alternating")
+    ap.add_argument("--reps", type=int, default=5, help="--onepass: timings per form")
     args = ap.parse_args()
     cfg = configs.get(args.config)
+    if args.onepass:
+        with torch.no_grad():
+            failed = onepass_rows(cfg, args, torch.device("cuda:0"))
+        sys.exit(1 if failed else 0)
     layers = workload.conv_flops_hot_path(cfg, args.size, args.size)["layers"]
     dev = torch.device("cuda:0")
     tot = {"fwd": [0.0, 0.0, 0.0], "dgrad": [0.0, 0.0, 0.0], "wgrad": [0.0, 0.0, 0.0]}

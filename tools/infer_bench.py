@@ -1,6 +1,10 @@
 #!/usr/bin/env python
-"""BASELINE config 5: bair 64x64 reconstruction-mode inference, batch 512, hipGraph-captured forward (kp detector on
-source + driving frames, generator).  Prints frames/s for eager launches and for graph replay."""
+"""Evaluation-mode forward (kp detector on source + driving frames, generator) through mnk.engine.Reconstructor.
+Default (BASELINE config 5): bair 64x64, batch 512 -- frames/s for eager launches and for hipGraph replay.
+--precision-ab: fp32 against the opt-in bf16 inference mode (precision="bf16": the 3x3 convolutions round their operands to
+bf16) at four configurations -- bair batch 512 @ 64 eager, moving-gif batch 64 @ 64, vox batch 8 @ 256, and the reference's
+batch-1 frame loop behind DataParallelWithCallback (mnk.dropin.EvalRunner under MNK_EVAL_PRECISION).  The two forms alternate,
+`--reps` timings each; median and spread (max - min) per form, one JSON line per configuration."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "monkey-net_amd"))
@@ -11,8 +15,79 @@ import bench
 ap = argparse.ArgumentParser()
 ap.add_argument("--config", default="bair"); ap.add_argument("--batch", type=int, default=512)
 ap.add_argument("--size", type=int, default=64); ap.add_argument("--iters", type=int, default=10)
+ap.add_argument("--precision-ab", action="store_true"); ap.add_argument("--reps", type=int, default=5)
+ap.add_argument("--only", default="", help="--precision-ab: comma-separated subset of bair,moving-gif,vox,frame-loop")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
+
+
+def timed(fn, iters):
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    for _ in range(iters):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / iters * 1e3
+
+
+def alternate(forms, iters, reps):
+    """forms: {name: callable}; -> {name: {"ms": median, "spread_ms": max - min}}, the forms timed in turn `reps` times"""
+    for fn in forms.values():
+        for _ in range(3):
+            fn()
+    times = {k: [] for k in forms}
+    for _ in range(reps):
+        for k, fn in forms.items():
+            times[k].append(timed(fn, iters))
+    return {k: {"ms": round(sorted(v)[len(v) // 2], 4), "spread_ms": round(max(v) - min(v), 4)} for k, v in times.items()}
+
+
+def reconstructor_ab(config, batch, size, iters):
+    gen, disc, kpd = bench.build_models(configs.get(config), dev)
+    src = torch.rand(batch, 3, 1, size, size, device=dev)
+    drv = torch.rand(batch, 3, 1, size, size, device=dev)
+    recs = {p: engine.Reconstructor(kpd, gen, precision=p) for p in ("fp32", "bf16")}
+    res = alternate({p: (lambda r=r: r(src, drv)) for p, r in recs.items()}, iters, args.reps)
+    a, b = recs["fp32"](src, drv)["video_prediction"], recs["bf16"](src, drv)["video_prediction"]
+    res["max_abs_prediction_difference"] = float((a - b).abs().max())
+    return {"workload": "%s Reconstructor eager, batch %d @ %dx%d" % (config, batch, size, size), **res,
+            "speedup": round(res["fp32"]["ms"] / res["bf16"]["ms"], 3)}
+
+
+def frame_loop_ab(config, size, frames, iters):
+    """reconstruction.py:45-62: both networks behind DataParallelWithCallback, one frame per call under no_grad"""
+    from sync_batchnorm import DataParallelWithCallback
+    gen, disc, kpd = bench.build_models(configs.get(config), dev)
+    generator, kp_detector = DataParallelWithCallback(gen), DataParallelWithCallback(kpd)
+    generator.eval(), kp_detector.eval()
+    video = torch.rand(1, 3, frames, size, size, device=dev)
+
+    def loop(precision):
+        os.environ["MNK_EVAL_PRECISION"] = precision
+        with torch.no_grad():
+            kp_source = kp_detector(video[:, :, :1])
+            for i in range(frames):
+                kp_driving = kp_detector(video[:, :, i:i + 1])
+                generator(source_image=video[:, :, :1], kp_driving=kp_driving, kp_source=kp_source)
+
+    res = alternate({p: (lambda p=p: loop(p)) for p in ("fp32", "bf16")}, iters, args.reps)
+    os.environ.pop("MNK_EVAL_PRECISION", None)
+    for v in (res["fp32"], res["bf16"]):
+        v["ms_per_frame"] = round(v["ms"] / frames, 4)
+    return {"workload": "%s frame loop through EvalRunner, batch 1 @ %dx%d, %d frames per loop" % (config, size, size, frames), **res,
+            "speedup": round(res["fp32"]["ms"] / res["bf16"]["ms"], 3)}
+
+
+if args.precision_ab:
+    only = set(filter(None, args.only.split(",")))
+    jobs = [("bair", lambda: reconstructor_ab("bair", 512, 64, args.iters)),
+            ("moving-gif", lambda: reconstructor_ab("moving-gif", 64, 64, args.iters)),
+            ("vox", lambda: reconstructor_ab("vox", 8, 256, max(2, args.iters // 2))),
+            ("frame-loop", lambda: frame_loop_ab("moving-gif", 64, 16, max(2, args.iters // 2)))]
+    for name, job in jobs:
+        if not only or name in only:
+            print(json.dumps(job()), flush=True)
+    sys.exit(0)
+
 gen, disc, kpd = bench.build_models(configs.get(args.config), dev)
 src = torch.rand(args.batch, 3, 1, args.size, args.size, device=dev)
 drv = torch.rand(args.batch, 3, 1, args.size, args.size, device=dev)
