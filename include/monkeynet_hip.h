@@ -352,6 +352,12 @@ typedef struct MnkWgradReduceDesc {
     int reserved;
 } MnkWgradReduceDesc;
 int mnk_wgrad_reduce_blocks(int splits, int Cout, int C);
+/* the thread map mnk_wgrad_reduce_multi takes for such a layer under the live "wgrad_reduce_vec", GIVEN that `part` is 16-byte
+ * aligned (the contract of the vector maps: a layer whose partials are not aligned is summed by the tile map, map 1, whatever
+ * this query says -- the same bits, slower):
+ * 0 flat float4 map, 1 tile map, 2 vector tap-major map, 3 vector parameter-major map; every map leaves the same bits, and
+ * mnk_wgrad_reduce_blocks covers whichever is taken (a table built under one tuning value is valid under the other) */
+int mnk_wgrad_reduce_map(int layout, int splits, int ntaps, int Cout, int C);
 /* the measured defaults of the launch plans (tile counts, split targets, rows per thread: `tuning_knob("name", ...)` in the
  * kernel sources, e.g. "split_tiles", "wgroup_chunk", "wtap_target", "bn_rpt") are not environment switches: a tuning script
  * sets one by name here; an A/B visit may pass them all in ONE environment variable, MNK_TUNING="name=value,name=value" */

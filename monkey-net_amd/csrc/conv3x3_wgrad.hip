@@ -1216,6 +1216,10 @@ __global__ void __launch_bounds__(256) conv3x3_wgrad_reduce_kernel(const float* 
 // rows): thread group g sums the splits g, g + groups, ... with 2 * ntaps independent loads in flight, the groups are
 // combined through LDS in a fixed order (deterministic), and the (tap, ci) -> (ci, tap) transposition of the tap-major
 // partials happens on the way into LDS.  blocks = ceil(Cout / rows) * ceil(C / tw) with (tw, rows) = reduce_map(splits).
+// That is the TILE map: a lane loads one float per (split, tap).  It fixes the sum of a gradient element; with
+// "wgrad_reduce_vec" = 1 (the default) the layers whose partials are cut into 16-byte quads take a vector map with the same
+// sums and float4 loads (reduce_map_id, reduce_vec_tap, reduce_param_major_vec below), which never needs more blocks than
+// the tile map -- surplus blocks return at once, and a table built under either value of the tuning value is valid under both.
 // thread map of one layer: channel-tile width tw and thread groups = 256 / tw
 //   splits <  4 : tw = 64, the 4 groups own 4 different output rows (each sums all its splits);
 //   splits < 32 : tw = 64, the 4 groups share one row and split the splits;
@@ -1229,7 +1233,7 @@ __host__ __device__ __forceinline__ void reduce_map(int splits, int* tw, int* ro
 // Few-split layers with C % 4 == 0 -- the deep levels (2x2 ... 8x8 maps, 256 ... 2048 channels), whose "partials" ARE the
 // gradient (240 of the 265 MB of BASELINE configs[1]) in tap-major order -- take a flat map instead: a thread owns four
 // consecutive input channels of one output row, reads one float4 per tap and split (1 KB contiguous per 64 lanes; the tile
-// map above reads 256-byte pieces: ~1.8 TB/s measured) and writes its 4 * ntaps consecutive gradient floats from registers:
+// map above reads 256-byte pieces: ~1.8 TB/s measured in round 3, before the vector maps below existed) and writes its 4 * ntaps consecutive gradient floats from registers:
 // no LDS, no barrier.  blocks = ceil(Cout * C / 4 / 256).
 __host__ __device__ __forceinline__ bool reduce_flat(int splits, int C) { return splits < 4 && (C & 3) == 0; }
 
@@ -1356,14 +1360,275 @@ __device__ __forceinline__ void reduce_param_major(const float* __restrict__ src
     }
 }
 
-// (four waves per SIMD: the kernel needs 132 registers unconstrained, i.e. three waves; capped at 128 it reduces the generator's
-// 692 MB of partials in 311 instead of 361 us; five waves -- 96 registers -- spill: 765 us.  tools/reduce_probe.py)
-__global__ void __launch_bounds__(256, 4) wgrad_reduce_multi_kernel(const MnkWgradReduceDesc* __restrict__ descs, int n) {
-    __shared__ float sm[16 * 16 * 16 + 64];        // [group][channel * ntaps + tap], group stride tw * 16
+// ---- vector thread maps ("wgrad_reduce_vec" = 1): the same sums, every global load a float4 -----------------------------------
+// The sum of one gradient element is what the maps above fix: G = 1 / 4 / 16 thread groups (splits < 4 / < 32 / >= 32), group g
+// owns the splits g, g + G, ... and adds them in two chains (its 1st, 3rd, ... and its 2nd, 4th, ... split, each in increasing
+// order from 0.f), the group's value is chain 0 + chain 1 (layout 2: up_fold of the group's 16 pseudo-tap values), the groups
+// are added in order from 0.f (one group: taken as it is), `accumulate` adds dw last.  Only which lane loads what changes, so
+// the results are the tile map's to the bit (tests/test_kernels_wgrad_reduce_vec.py).
+enum { REDUCE_MAP_FLAT = 0, REDUCE_MAP_TILE = 1, REDUCE_MAP_VEC_TAP = 2, REDUCE_MAP_VEC_PARAM = 3 };
+static int g_wgrad_reduce_vec = tuning_knob("wgrad_reduce_vec", &g_wgrad_reduce_vec, 1);      // 0: the flat and tile maps only
+
+// which map a descriptor takes.  Contract: `part` is 16-byte aligned (mnk/optim.py's partial buffers are whole allocations);
+// the kernel checks, and a layer whose partials are not keeps the tile map -- same bits, none of the speed, and
+// mnk_wgrad_reduce_map, which sees no pointer, still names the vector map (tests/test_kernels_wgrad_reduce_vec.py runs one).
+// On the 4- and 16-group maps a block covers four times the tile map's floats, so three quarters of such a layer's blocks
+// (mnk_wgrad_reduce_blocks cannot know the layout) find their descriptor and return.
+//   tap-major, (Cout * C) % 4 == 0, 3x3 / 4x4 taps: the [co][ci] plane of a (split, tap) is cut into quads regardless of rows
+//   parameter-major, (C * ntaps) % 4 == 0: the tile map's tiles, read as quads along the gradient-ordered axis
+// (the 45 -> 45 layers' planes of 2025 floats stay on the tile map)
+__host__ __device__ __forceinline__ int reduce_map_id(int vec, int layout, int splits, int ntaps, int Cout, int C) {
+    if (reduce_flat(splits, C) && (ntaps == 9 || ntaps == 16)) return REDUCE_MAP_FLAT;
+    if (!vec) return REDUCE_MAP_TILE;
+    if (layout == 1) return (((long)C * ntaps) & 3) == 0 ? REDUCE_MAP_VEC_PARAM : REDUCE_MAP_TILE;
+    const long plane = (long)Cout * C;
+    // (measured per class, profiles/wgrad_reduce_vec_ab.txt: the sub-pixel form with 4 ... 31 splits is the one class that is
+    // slower on the vector map -- five of its six flagship layers, 5.5 ... 7.7 -> 8.1 ... 9.7 us alone -- and keeps the tile map)
+    const bool taps_ok = layout == 2 ? (ntaps == 9 && (splits < 4 || splits >= 32)) : (layout == 0 && (ntaps == 9 || ntaps == 16));
+    const int G = splits < 4 ? 1 : (splits < 32 ? 4 : 16), nin = layout == 2 ? 16 : ntaps;
+    // (a lane's share of an address -- its group's first split and its quad -- is a 32-bit byte offset: reduce_vec_tap)
+    return (taps_ok && (plane & 3) == 0 && ((long)(G - 1) * nin + 1) * plane < (1L << 30)) ? REDUCE_MAP_VEC_TAP : REDUCE_MAP_TILE;
+}
+
+__device__ __forceinline__ void add4(float4& a, const float4& x) { a = make_float4(a.x + x.x, a.y + x.y, a.z + x.z, a.w + x.w); }
+
+// r[i] = chain 0 + chain 1 of the float4 at tap i over the group's splits g, g + G, ...: the k-th of them is read at
+// ub + k * gstep + i * plane (block-uniform: scalar registers) + voff bytes (the lane's part, g * sstride + its quad: ONE vector
+// register -- a 64-bit lane pointer per (split, tap) in flight made the kernel spill).  U = 2: four splits' loads are issued
+// before the first add of a trip (the adds of a chain stay in split order)
+__device__ __forceinline__ float4 vec_ld(const float* __restrict__ u, unsigned voff) {
+#ifdef HIPEMU
+    return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(u) + voff);
+#else
+    // partials are global memory, but a pointer read from the table is generic to the compiler (flat_load, a vector pointer
+    // pair per address): say so, and the load takes its base from scalar registers
+    typedef float f4v __attribute__((ext_vector_type(4)));
+    typedef const __attribute__((address_space(1))) char* gchar;
+    const f4v v = *reinterpret_cast<const __attribute__((address_space(1))) f4v*>((gchar)(const char*)u + voff);
+    return make_float4(v.x, v.y, v.z, v.w);
+#endif
+}
+template <int TP, int U>
+__device__ __forceinline__ void vec_chain_pass(const float* __restrict__ ub, unsigned voff, long gstep, long plane, int splits,
+                                               int g, int G, float4* r) {
+    float4 a0[TP], a1[TP];
+#pragma unroll
+    for (int i = 0; i < TP; ++i) a0[i] = a1[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    int k = 0;
+    if (U == 2) {
+        for (; g + (k + 3) * G < splits; k += 4) {
+            const float* p0 = ub + (long)k * gstep;
+            const float* p1 = p0 + gstep;
+            const float* p2 = p1 + gstep;
+            const float* p3 = p2 + gstep;
+            float4 x0[TP], x1[TP], x2[TP], x3[TP];
+#pragma unroll
+            for (int i = 0; i < TP; ++i) {
+                x0[i] = vec_ld(p0 + (long)i * plane, voff);
+                x1[i] = vec_ld(p1 + (long)i * plane, voff);
+                x2[i] = vec_ld(p2 + (long)i * plane, voff);
+                x3[i] = vec_ld(p3 + (long)i * plane, voff);
+            }
+#pragma unroll
+            for (int i = 0; i < TP; ++i) {
+                add4(a0[i], x0[i]);
+                add4(a1[i], x1[i]);
+                add4(a0[i], x2[i]);
+                add4(a1[i], x3[i]);
+            }
+        }
+    }
+    for (; g + (k + 1) * G < splits; k += 2) {
+        const float* p0 = ub + (long)k * gstep;
+        const float* p1 = p0 + gstep;
+        float4 x0[TP], x1[TP];
+#pragma unroll
+        for (int i = 0; i < TP; ++i) {
+            x0[i] = vec_ld(p0 + (long)i * plane, voff);
+            x1[i] = vec_ld(p1 + (long)i * plane, voff);
+        }
+#pragma unroll
+        for (int i = 0; i < TP; ++i) {
+            add4(a0[i], x0[i]);
+            add4(a1[i], x1[i]);
+        }
+    }
+    if (g + k * G < splits) {
+        const float* p0 = ub + (long)k * gstep;
+#pragma unroll
+        for (int i = 0; i < TP; ++i) add4(a0[i], vec_ld(p0 + (long)i * plane, voff));
+    }
+#pragma unroll
+    for (int i = 0; i < TP; ++i) r[i] = make_float4(a0[i].x + a1[i].x, a0[i].y + a1[i].y, a0[i].z + a1[i].z, a0[i].w + a1[i].w);
+}
+
+// LDS of the vector tap-major map: [group][quad][4 elements][NB taps], quad stride 4 * NB + 1 (odd: the lanes of a group write
+// different banks); groups * quads per group = 256, so 256 * 37 floats with NB = 9
+#define REDUCE_VEC_QS(NB) (4 * (NB) + 1)
+#define REDUCE_SM_FLOATS (256 * REDUCE_VEC_QS(9))
+
+template <int NB>
+__device__ __forceinline__ void vec_put(float* __restrict__ smq, int j, const float4& v) {
+    smq[0 * NB + j] = v.x;
+    smq[1 * NB + j] = v.y;
+    smq[2 * NB + j] = v.z;
+    smq[3 * NB + j] = v.w;
+}
+
+// the block's 4 * qw plane elements x NB taps (gradient taps tb0 ...): groups added in order, stored as runs of NB floats per
+// element -- consecutive threads write consecutive floats of a dw row whatever the slice's alignment
+template <int NB>
+__device__ __forceinline__ void vec_sum_groups_store(const MnkWgradReduceDesc& d, const float* __restrict__ sm, int groups, int qw,
+                                                     unsigned p0, unsigned plane, int tb0) {
+    constexpr int QS = REDUCE_VEC_QS(NB);
+    const int n_out = qw * 4 * NB, gstride = qw * QS;
+    for (int idx = threadIdx.x; idx < n_out; idx += 256) {
+        const int q = idx / (4 * NB), r = idx - q * (4 * NB), k = r / NB, j = r - k * NB;
+        const unsigned p = p0 + 4 * q + k;
+        if (p >= plane) break;                                   // (p does not decrease with idx)
+        const unsigned co = p / (unsigned)d.C, ci = p - co * (unsigned)d.C;
+        const float* s = sm + q * QS + r;
+        float v;
+        if (groups == 1) {
+            v = s[0];
+        } else {
+            v = 0.f;
+            for (int gg = 0; gg < groups; ++gg) v += s[gg * gstride];       // fixed order: deterministic
+        }
+        float* dst = d.dw + ((long)co * d.Cin_total + d.c_start + ci) * d.ntaps + tb0 + j;
+        *dst = d.accumulate ? *dst + v : v;
+    }
+}
+
+// tap-major partials part[s][tap][co][ci] (layout 2: 16 pseudo taps) on the vector map: block `local` owns the 1024 / G plane
+// floats from local * 1024 / G on, a lane one quad of them for its group's splits.  The taps go in passes of three or four (16
+// taps x two chains x float4 do not fit in 128 registers; different taps are different bytes, nothing is read twice); the
+// sub-pixel form's pass is one phase (pseudo taps 4 * phase ...), folded into the nine kernel taps as up_fold does: phase by
+// phase from 0.f.
+__device__ __forceinline__ void reduce_vec_tap(const MnkWgradReduceDesc& d, int local, float* __restrict__ sm) {
+    const int groups = d.splits < 4 ? 1 : (d.splits < 32 ? 4 : 16), qw = 256 / groups;
+    const unsigned plane = (unsigned)d.Cout * (unsigned)d.C;
+    const unsigned p0 = (unsigned)local * (unsigned)(4 * qw);
+    if (p0 >= plane) return;                                     // a surplus block (block-uniform: no barrier is missed)
+    const int t = threadIdx.x, g = t / qw, q = t - g * qw;
+    const bool ok = p0 + 4 * q < plane;
+    const int nin = d.layout == 2 ? 16 : d.ntaps;
+    const long sstride = (long)nin * plane;
+    const float* src = d.part + p0;                              // block-uniform
+    // the lane's part of every address, in bytes (< 2^32: reduce_map_id; lanes past the plane read the block's first quad)
+    const unsigned voff = (unsigned)(((long)g * sstride + (ok ? 4 * q : 0)) * 4);
+    const long gstep = (long)groups * sstride;
+    if (d.layout == 2) {
+        float4 f[9];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) f[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 1
+        for (int ph = 0; ph < 4; ++ph) {                        // (not unrolled: four copies of the split loop spill)
+            float4 r[4];
+            vec_chain_pass<4, 1>(src + (long)(4 * ph) * plane, voff, gstep, plane, d.splits, g, groups, r);
+            // up_fold_pairs: phase (a, b) = (ph >> 1, ph & 1) gives kernel row 0 its pseudo taps u = 0, row 2 u = 1, row 1
+            // u = 1 if a == 0 else 0; columns likewise with b and v.  Pseudo tap (u, v) is r[2 * u + v].
+            const bool a0 = (ph >> 1) == 0, b0 = (ph & 1) == 0;
+            const float4 m0 = a0 ? r[2] : r[0], m1 = a0 ? r[3] : r[1];
+            const float4 row[3][2] = {{r[0], r[1]}, {m0, m1}, {r[2], r[3]}};
+#pragma unroll
+            for (int ky = 0; ky < 3; ++ky) {
+                add4(f[ky * 3 + 0], row[ky][0]);
+                add4(f[ky * 3 + 1], b0 ? row[ky][1] : row[ky][0]);
+                add4(f[ky * 3 + 2], row[ky][1]);
+            }
+        }
+        float* smq = sm + (g * qw + q) * REDUCE_VEC_QS(9);
+#pragma unroll
+        for (int i = 0; i < 9; ++i) vec_put<9>(smq, i, f[i]);
+        __syncthreads();
+        vec_sum_groups_store<9>(d, sm, groups, qw, p0, plane, 0);
+    } else if (d.ntaps == 9) {
+        float* smq = sm + (g * qw + q) * REDUCE_VEC_QS(9);
+#pragma unroll
+        for (int ps = 0; ps < 3; ++ps) {
+            float4 r[3];
+            vec_chain_pass<3, 2>(src + (long)(3 * ps) * plane, voff, gstep, plane, d.splits, g, groups, r);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) vec_put<9>(smq, 3 * ps + i, r[i]);
+        }
+        __syncthreads();
+        vec_sum_groups_store<9>(d, sm, groups, qw, p0, plane, 0);
+    } else {                                                     // 16 taps: two batches of eight (the LDS holds nine per element)
+        float* smq = sm + (g * qw + q) * REDUCE_VEC_QS(8);
+        for (int tb = 0; tb < 16; tb += 8) {
+#pragma unroll
+            for (int ps = 0; ps < 2; ++ps) {
+                float4 r[4];
+                vec_chain_pass<4, 1>(src + (long)(tb + 4 * ps) * plane, voff, gstep, plane, d.splits, g, groups, r);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) vec_put<8>(smq, 4 * ps + i, r[i]);
+            }
+            __syncthreads();
+            vec_sum_groups_store<8>(d, sm, groups, qw, p0, plane, tb);
+            __syncthreads();
+        }
+    }
+}
+
+// parameter-major partials on the vector map: the tile map's tile (lim = cw * ntaps contiguous floats, a multiple of four that
+// starts on a quad), this thread's quads c, c + TW, ... (those below `nq`) summed over the splits s0, s0 + sstep, ... into
+// out[4 * c ...], out[4 * (c + TW) ...]: per element the sums of reduce_param_major
+template <int TW>
+__device__ __forceinline__ void reduce_param_major_vec(const float* __restrict__ src, long sstride, int splits, int s0, int sstep,
+                                                       int nq, bool row_ok, float* __restrict__ out) {
+    const int nk = (nq + TW - 1) / TW;                           // quads of this thread (<= 0: none)
+    for (int k0 = 0; k0 < nk; k0 += 4) {                         // four quads x two splits in flight
+        float4 a0[4], a1[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) a0[k] = a1[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+        const float* sk = src + (long)k0 * TW * 4;
+        int sp = s0;
+        for (; sp + sstep < splits; sp += 2 * sstep) {
+            const float* ps = sk + (long)sp * sstride;
+            const float* pt = ps + (long)sstep * sstride;
+            float4 x0[4], x1[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k0 + k < nk) {
+                    x0[k] = *reinterpret_cast<const float4*>(ps + k * TW * 4);
+                    x1[k] = *reinterpret_cast<const float4*>(pt + k * TW * 4);
+                }
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k0 + k < nk) {
+                    add4(a0[k], x0[k]);
+                    add4(a1[k], x1[k]);
+                }
+        }
+        if (sp < splits) {
+            const float* ps = sk + (long)sp * sstride;
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k0 + k < nk) add4(a0[k], *reinterpret_cast<const float4*>(ps + k * TW * 4));
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (k0 + k < nk)
+                *reinterpret_cast<float4*>(out + (long)(k0 + k) * TW * 4) =
+                    row_ok ? make_float4(a0[k].x + a1[k].x, a0[k].y + a1[k].y, a0[k].z + a1[k].z, a0[k].w + a1[k].w)
+                           : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
+// (four waves per SIMD.  The parent of the vector maps needed 132 registers unconstrained, i.e. three waves; capped at 128 it
+// reduced the generator's 692 MB of partials in 311 instead of 361 us, and five waves -- 96 registers -- spilled: 765 us.  With
+// the vector maps: 128 registers, no scratch, 37892 bytes of LDS -- four blocks are 151.6 of a CU's 160 KB, so REDUCE_SM_FLOATS
+// has no room to grow: 2 KB more per block and only three blocks are resident -- and the same 692 MB in 219 us, the
+// discriminator's 179 MB in 40 instead of 91 us.  tools/reduce_probe.py, tools/isa_report.py, profiles/wgrad_reduce_vec_ab.txt)
+__global__ void __launch_bounds__(256, 4) wgrad_reduce_multi_kernel(const MnkWgradReduceDesc* __restrict__ descs, int n, int vec) {
+    // tile map: [group][channel * ntaps + tap], group stride tw * 16 (16 * 16 * 16 + 64 floats); vector map: reduce_vec_tap
+    __shared__ __attribute__((aligned(16))) float sm[REDUCE_SM_FLOATS];
     __shared__ int sh_idx;
     const int b = blockIdx.x;
     const int di = find_desc(&descs[0].block_begin, (int)(sizeof(MnkWgradReduceDesc) / sizeof(int)), n, b, &sh_idx);
-    const MnkWgradReduceDesc d = descs[di];
+    // (the descriptor is block-uniform: scalar registers -- as vector registers its 14 words made the vector maps spill)
+    const MnkWgradReduceDesc d = descs[__builtin_amdgcn_readfirstlane(di)];
     const int local = b - d.block_begin;
     if (reduce_flat(d.splits, d.C) && (d.ntaps == 9 || d.ntaps == 16)) {      // (block-uniform: no barrier follows on this path)
         const int q4 = d.C >> 2;
@@ -1380,6 +1645,12 @@ __global__ void __launch_bounds__(256, 4) wgrad_reduce_multi_kernel(const MnkWgr
             reduce_flat_body<9, 9, 1>(d, co, ci);
         else
             reduce_flat_body<16, 16, 1>(d, co, ci);
+        return;
+    }
+    // (block-uniform; unaligned partials -- no caller of this library has them -- keep the tile map)
+    const int map = ((size_t)d.part & 15) == 0 ? reduce_map_id(vec, d.layout, d.splits, d.ntaps, d.Cout, d.C) : REDUCE_MAP_TILE;
+    if (map == REDUCE_MAP_VEC_TAP) {
+        reduce_vec_tap(d, local, sm);
         return;
     }
     int tw, rpb;
@@ -1438,7 +1709,12 @@ __global__ void __launch_bounds__(256, 4) wgrad_reduce_multi_kernel(const MnkWgr
         // and walks the splits with eight of them in flight (one at a time meant two loads in flight and ntaps passes over
         // the splits: the 512-split 45 -> 45 layers' blocks were the tail of the launch)
         const float* src = d.part + (long)(row_ok ? co : 0) * NT + (long)ci0 * ntaps + c;
-        if (tw == 16)
+        if (map == REDUCE_MAP_VEC_PARAM) {
+            if (tw == 16)
+                reduce_param_major_vec<16>(src + 3 * c, sstride, d.splits, s0, sstep, (lim >> 2) - c, row_ok, smg + 4 * c);
+            else
+                reduce_param_major_vec<64>(src + 3 * c, sstride, d.splits, s0, sstep, (lim >> 2) - c, row_ok, smg + 4 * c);
+        } else if (tw == 16)
             reduce_param_major<16>(src, sstride, d.splits, s0, sstep, lim - c, row_ok, smg + c);
         else
             reduce_param_major<64>(src, sstride, d.splits, s0, sstep, lim - c, row_ok, smg + c);
@@ -2134,11 +2410,16 @@ int mnk_wgrad_reduce_blocks(int splits, int Cout, int C) {
     return ceil_div(Cout, rows) * ceil_div(C, tw);
 }
 
+int mnk_wgrad_reduce_map(int layout, int splits, int ntaps, int Cout, int C) {
+    if (splits <= 0 || Cout <= 0 || C <= 0 || ntaps <= 0) return -1;
+    return reduce_map_id(g_wgrad_reduce_vec != 0, layout, splits, ntaps, Cout, C);
+}
+
 int mnk_wgrad_reduce_multi(const MnkWgradReduceDesc* descs_device, int n, int total_blocks, void* stream) {
     MNK_REQUIRE(descs_device && n > 0 && total_blocks > 0);
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(K_CONV_REDUCE, s, 0.0);
-    hipLaunchKernelGGL(wgrad_reduce_multi_kernel, dim3(total_blocks), dim3(256), 0, s, descs_device, n);
+    hipLaunchKernelGGL(wgrad_reduce_multi_kernel, dim3(total_blocks), dim3(256), 0, s, descs_device, n, g_wgrad_reduce_vec != 0);
     MNK_LAUNCH_CHECK();
     return MNK_OK;
 }
