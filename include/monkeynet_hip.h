@@ -66,6 +66,8 @@ int mnk_copy_channels(const float* src, int ld_src, int src_off, float* dst, int
 /* torch.cat([a, b], dim=channel) on acts in one launch, pad channels written (modules/util.py:185 the last decoder stage;
  * discriminator.py:50-52 the key-point heat-maps behind the frame): out[n][p] = [a[n][p][0..ca) | b[n mod Nb][p][0..cb) | 0...],
  * Nb = N, or N / 2 for the batched [generated | real] discriminator pass that embeds the same key points for both halves.
+ * Columns [0, min(round_up(ca + cb, 4), ld_out)) of every row of out are written; a wider ld_out is a view into a larger act,
+ * whose other columns are left alone.
  * Adjoint: ga = [g[..][0..ca) | 0...]; gb (may be NULL) [m][p] = [g[m][p][ca..) + g[m + Nb][p][ca..) + ... | 0...]. */
 int mnk_concat2_fwd(const float* a, int ld_a, int ca, const float* b, int ld_b, int cb, int Nb, float* out, int ld_out, int N,
                     long rows_per_frame, void* stream);

@@ -86,11 +86,11 @@ __global__ void __launch_bounds__(256) copy_channels_kernel(const float* __restr
 // (Nb < N: the batched discriminator pass [generated | real] embeds the same key points for both halves)
 __global__ void __launch_bounds__(256) concat2_fwd_kernel(const float* __restrict__ a, int ld_a, int ca,
                                                           const float* __restrict__ b, int ld_b, int cb, int Nb,
-                                                          float* __restrict__ out, int ld_out, int N, long rpf) {
-    const long total = (long)N * rpf * ld_out;
+                                                          float* __restrict__ out, int ld_out, int wo, int N, long rpf) {
+    const long total = (long)N * rpf * wo;      // wo = round_up(ca + cb, 4) columns of a row; the rest of ld_out is not ours
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int c = (int)(i % ld_out);
-        const long r = i / ld_out;
+        const int c = (int)(i % wo);
+        const long r = i / wo;
         float v = 0.f;
         if (c < ca) {
             v = a[r * ld_a + c];
@@ -98,7 +98,7 @@ __global__ void __launch_bounds__(256) concat2_fwd_kernel(const float* __restric
             const long n = r / rpf, p = r - n * rpf;
             v = b[((n % Nb) * rpf + p) * ld_b + c - ca];
         }
-        out[i] = v;
+        out[r * ld_out + c] = v;
     }
 }
 
@@ -352,10 +352,11 @@ int mnk_concat2_fwd(const float* a, int ld_a, int ca, const float* b, int ld_b, 
     MNK_REQUIRE(a && b && out && ca > 0 && cb > 0 && ca <= ld_a && cb <= ld_b && ca + cb <= ld_out && N > 0 && Nb > 0 &&
                 N % Nb == 0 && rows_per_frame > 0);
     hipStream_t s = (hipStream_t)stream;
-    const long total = (long)N * rows_per_frame * ld_out;
+    const int wo = mnk::round_up(ca + cb, 4) < ld_out ? mnk::round_up(ca + cb, 4) : ld_out;   // a wider act's other columns stay
+    const long total = (long)N * rows_per_frame * wo;
     ProfScope prof(K_LAYOUT, s, (double)total * 8);
-    hipLaunchKernelGGL(concat2_fwd_kernel, dim3(grid_for(total, 8192)), dim3(256), 0, s, a, ld_a, ca, b, ld_b, cb, Nb, out, ld_out, N,
-                       rows_per_frame);
+    hipLaunchKernelGGL(concat2_fwd_kernel, dim3(grid_for(total, 8192)), dim3(256), 0, s, a, ld_a, ca, b, ld_b, cb, Nb, out, ld_out, wo,
+                       N, rows_per_frame);
     MNK_LAUNCH_CHECK();
     return MNK_OK;
 }

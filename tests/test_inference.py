@@ -124,7 +124,7 @@ def test_batched_transfer_equals_the_frame_loop_and_normalize_kp_its_formulas(be
     import numpy as np
     from scipy.spatial import ConvexHull
     from mnk import engine
-    from modules.util import matrix_inverse
+    from _kp_restate import normalize_kp_fp64
     gold = load("tiny")
     gen, disc, kpd = build(gold["cfg"])
     gen.load_state_dict(gold["state"]["generator"]), kpd.load_state_dict(gold["state"]["kp_detector"])
@@ -140,12 +140,7 @@ def test_batched_transfer_equals_the_frame_loop_and_normalize_kp_its_formulas(be
         kp_s = kpd(src)
         mv, vv, ma, va = (t.cpu().double() for t in (kp_d["mean"], kp_d["var"], kp_s["mean"], kp_s["var"]))
         mult = np.sqrt(ConvexHull(ma[0, 0].numpy()).volume) / np.sqrt(ConvexHull(mv[0, 0].numpy()).volume)
-        mean = ((mv - mv[:, 0:1]) * mult + ma).clamp(-1, 1)
-        var = torch.matmul(torch.matmul(vv, matrix_inverse(vv[:, 0:1])), va)
-        sym = (var + var.transpose(-1, -2)) / 2
-        ev, eu = np.linalg.eigh(sym.numpy())
-        ev[ev <= 0] = 1e-6
-        var = torch.from_numpy(np.einsum("...ij,...j,...kj->...ik", eu, ev, eu))
+        mean, var = normalize_kp_fp64(mv, vv, ma, va, mult, move_location=True, clip_mean=True, adapt_variance=True)
         assert float((got["kp_norm"]["mean"].cpu().double() - mean).abs().max()) < 2e-6
         assert float((got["kp_norm"]["var"].cpu().double() - var).abs().max()) < 2e-6
         frames = []

@@ -24,7 +24,9 @@ from _guard import be  # noqa: F401  (guard-banded buffers, checked calls)
 from _util import to_nhwc, from_nhwc, ceil4
 import test_kernels_bn as kbn
 import test_kernels_conv as kc
+import test_kernels_conv1x1_fast as k11
 import test_kernels_motion as kmo
+import test_multiframe_kernels as kmf
 import test_predictor as kpr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -77,6 +79,23 @@ WS_CASES = [
     ("deform-backward", lambda be: kmo.test_deform(be, "wide", (2, 300, 4, 4), 0), {"mnk_deform_bwd"}),
     ("gru-gemm-splitk", lambda be: kpr.test_gemm_against_fp64(be, 1, 0, 40, 24, 1100, False), {"mnk_gru_gemm"}),
     ("gru-colsum", lambda be: kpr.test_colsum_against_fp64(be), {"mnk_gru_colsum"}),
+    # the warps of all levels in one launch; C = 300 takes channel slices, i.e. the most workspace per pixel
+    ("warp-levels-backward", lambda be: kmo.test_warp_levels_direct(be, "edges", 0, "all"), {"mnk_warp_levels_bwd"}),
+    ("warp-levels-shared-backward", lambda be: kmf.test_shared_source_equals_the_repeated_source_all_levels(be, *kmf.SHARED_CASES[4]),
+     {"mnk_warp_levels_shared_bwd"}),
+    ("deform-shared-backward", lambda be: kmf.test_shared_source_equals_the_repeated_source_per_level(be, *kmf.SHARED_CASES[4]),
+     {"mnk_deform_shared_bwd"}),
+    ("bn-apply-colsum", lambda be: kbn.test_bn_train_forward_backward(be, (3, 45, 4, 6), 0), {"mnk_bn_act_bwd_apply_colsum"}),
+    ("bn-apply-add-colsum", lambda be: kbn.test_bn_backward_apply_adds_the_skip_gradient(be, (1, 64, 16, 16), 1),
+     {"mnk_bn_act_bwd_apply_add_colsum"}),
+    ("bn-stats-finalize", lambda be: kbn.test_bn_train_forward_backward(be, (2, 300, 2, 2), 0), {"mnk_bn_stats_finalize"}),
+    ("norm-backward-stats", lambda be: kbn.test_instance_norm_leaky_pool(be, (3, 12, 13, 13), 0), {"mnk_norm_act_bwd_stats"}),
+    ("conv1x1-head-two-row-blocks", lambda be: k11.test_head_weight_gradient_with_one_and_with_two_row_blocks(
+        be, (18, 11), 70, 0, 2, 0), {"mnk_conv1x1_bwd"}),
+    ("kxk-4x4-wgrad", lambda be: kc.test_conv4x4_nopad_forward_dgrad_wgrad(be, kc.K4_CASES[0], 0), {"mnk_conv2d_wgrad"}),
+    # the sub-pixel data gradient at BNSTATS_CASES[4]'s sizes: few tiles and K = 16 taps x 9 chunks, so the plan splits K
+    ("subpixel-dgrad-bnstats-splitk", lambda be: kc.test_data_gradient_leaves_the_backward_statistics_of_the_norm_layer_in_front(
+        be, (2, 4, 4, 136, 24, True, False, 0.0)), {"mnk_conv3x3_up_dgrad_bnstats"}),
 ]
 
 

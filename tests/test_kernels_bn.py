@@ -72,6 +72,61 @@ def test_bn_train_forward_backward(be, shape, pool):
     assert maxerr(dys.cpu(), ref_sum) <= 1e-5 * float(DY.cpu().abs().double().reshape(-1, ld).sum(0).max()) + 1e-6
 
 
+@pytest.mark.parametrize("shape", [(2, 5, 6, 4), (3, 45, 4, 6), (2, 300, 2, 2), (1, 64, 16, 16)])
+@pytest.mark.parametrize("pool", [0, 1])
+def test_bn_backward_apply_adds_the_skip_gradient(be, shape, pool):
+    """mnk_bn_act_bwd_apply_add_colsum (a residual block's first norm layer, util.py:58-67 `out += x`) at
+    test_bn_train_forward_backward's shapes: dy = the _colsum form's dy + the skip gradient (and the fp64 autograd gradient of
+    relu(bn(x)) [pooled] plus it, both within that test's 1e-4), the column sums over the sum within that test's bound; with an
+    all-zero skip gradient the _colsum form's dy and column sums bit for bit.  The addend's rows are wider than the act
+    (ld_add = ld + 4, NaN behind the act's channels: never read)."""
+    n, c, h, w = shape
+    g = torch.Generator().manual_seed(3)
+    x = torch.randn(n, c, h, w, generator=g) * 2 + 0.5
+    gamma, beta = torch.rand(c, generator=g) + 0.5, torch.randn(c, generator=g) * 0.3
+    xd = x.double().requires_grad_(True)
+    z = F.relu(F.batch_norm(xd, None, None, gamma.double(), beta.double(), True, 0.1, 1e-5))
+    if pool:
+        z = F.avg_pool2d(z, 2)
+    dz = torch.randn(z.shape, generator=g, dtype=torch.float64)
+    z.backward(dz)
+    skip = torch.randn(n, c, h, w, generator=g)
+    ld, rows = ceil4(c), n * h * w
+    lda = ld + 4
+    X, G, Bt = be.t(to_nhwc(x)), be.t(gamma), be.t(beta)
+    nws = be.query("mnk_bn_workspace_floats", rows, ld)
+    ws, sums = be.empty(nws), be.empty(2 * c)
+    be.call("mnk_bn_stats", X, ld, rows, c, sums, ws, nws)
+    mean, invstd, scale = be.empty(c), be.empty(c), be.empty(c)
+    be.call("mnk_bn_finalize", sums, float(rows), G, be.zeros(c), be.zeros(c) + 1, 0.1, 1e-5, c, 1, mean, invstd, scale)
+    DZ = be.t(to_nhwc(dz.float()))
+    bs = be.empty(2 * c)
+    be.call("mnk_bn_act_bwd_stats", X, ld, DZ, ld, 0, mean, invstd, scale, Bt, n, h, w, c, 1, pool, bs, ws, nws)
+    add = torch.full((n, h, w, lda), float("nan"))
+    add[..., :ld] = to_nhwc(skip)
+    zero = torch.full((n, h, w, lda), float("nan"))
+    zero[..., :ld] = 0
+    ADD, ZERO = be.t(add), be.t(zero)
+    DY0, DY1, DY2 = (be.empty(n, h, w, ld) for _ in range(3))
+    s0, s1, s2 = be.empty(c), be.empty(c), be.empty(c)
+    tail = (n, h, w, c, 1, pool)
+    be.call("mnk_bn_act_bwd_apply_colsum", X, ld, DZ, ld, 0, mean, invstd, scale, Bt, bs, float(rows), 1, DY0, ld, *tail, s0,
+            be.empty(nws), nws)
+    be.call("mnk_bn_act_bwd_apply_add_colsum", X, ld, DZ, ld, 0, mean, invstd, scale, Bt, bs, float(rows), 1, ZERO, lda, DY1, ld,
+            *tail, s1, be.empty(nws), nws)
+    be.call("mnk_bn_act_bwd_apply_add_colsum", X, ld, DZ, ld, 0, mean, invstd, scale, Bt, bs, float(rows), 1, ADD, lda, DY2, ld,
+            *tail, s2, be.empty(nws), nws)
+    be.sync()
+    d0, d2 = DY0.cpu(), DY2.cpu()
+    assert relerr(from_nhwc(d0, c), xd.grad) < 1e-4
+    assert torch.equal(DY1.cpu(), d0) and torch.equal(s1.cpu().view(torch.int32), s0.cpu().view(torch.int32))
+    assert relerr(from_nhwc(d2, c), from_nhwc(d0, c).double() + skip.double()) < 1e-4
+    assert relerr(from_nhwc(d2, c), xd.grad + skip.double()) < 1e-4
+    assert torch.all(d2[..., c:] == 0)
+    want = d2.double().reshape(-1, ld).sum(0)[:c]              # of the written dy, as in test_bn_train_forward_backward
+    assert maxerr(s2.cpu(), want) <= 1e-5 * float(d2.abs().double().reshape(-1, ld).sum(0).max()) + 1e-6
+
+
 @pytest.mark.parametrize("row_blocks", [1, 63, 257, 700, 2048])
 def test_second_stage_over_many_row_block_partials(be, row_blocks):
     """The second stage alone (mnk_bn_stats_finish, and fused with the finalisation: mnk_bn_stats_finalize on partials a conv

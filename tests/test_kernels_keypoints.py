@@ -125,6 +125,40 @@ def test_movement_embedding(be, name, d):
             assert relerr(dvs.view(b, d, K, 2, 2).sum(1, keepdim=True), ks64["var"].grad) < tol
 
 
+@pytest.mark.parametrize("name,d,hw,spread", [("mask", 1, (16, 16), 0.6), ("mask_diff", 3, (16, 12), 0.6), ("sum", 2, (9, 13), 1.2)])
+def test_movement_embedding_image_gradient_direct(be, name, d, hw, spread):
+    """mnk_movement_embedding_img_bwd called directly on guard-banded buffers (test_embedding_image_gradient reaches it through
+    the module, which allocates from torch's pool): d source image against the fp64 autograd of restate.movement_embedding,
+    within that test's bound; every element of dimg written, pad channels 0; the same bits on a second run."""
+    p = dict(VARIANTS[name], num_kp=4, kp_variance="matrix", num_channels=3)
+    g = torch.Generator().manual_seed(8)
+    b, K, c = 2, 4, 3
+    h, w = hw
+    src = torch.rand(b, c, 1, h, w, generator=g)
+    kpd, kps = cases.random_kp(b, d, K, seed=6, spread=spread), cases.random_kp(b, 1, K, seed=7, spread=spread)
+    s64 = src.double().requires_grad_(True)
+    ref = restate.movement_embedding(p, s64, {k: v.double() for k, v in kpd.items()}, {k: v.double() for k, v in kps.items()})
+    cemb = ref.shape[1]
+    dref = torch.randn(ref.shape, generator=g, dtype=torch.float64)
+    (ref * dref).sum().backward()
+    ld_out, ld_img = ceil4(cemb), ceil4(c)
+    dout = torch.zeros(b * d, h, w, ld_out)
+    dout[..., :cemb] = dref.permute(0, 2, 3, 4, 1).reshape(b * d, h, w, cemb).float()
+    MD, MS, DO = be.t(kpd["mean"].reshape(b * d, K, 2)), be.t(kps["mean"].reshape(b, K, 2)), be.t(dout)
+    add_bg, uh, ud = int(p.get("add_bg_feature_map", False)), int(p.get("use_heatmap", True)), int(p.get("use_difference", False))
+    runs = []
+    for _ in range(2):
+        DI = be.empty(b, h, w, ld_img)
+        be.call("mnk_movement_embedding_img_bwd", ld_img, c, MD, MS, b, d, h, w, K, add_bg, uh, ud, DO, ld_out, DI)
+        be.sync()
+        runs.append(DI.cpu())
+    assert torch.equal(runs[0].view(torch.int32), runs[1].view(torch.int32))
+    assert torch.all(runs[0][..., c:] == 0)
+    err = relerr(from_nhwc(runs[0], c), s64.grad[:, :, 0])
+    print("%s d=%d: relerr(d source) = %.3e" % (name, d, err))
+    assert err < 1e-5
+
+
 def test_embedding_matches_reference_golden(be):
     """The committed outputs of the REAL reference module (tests/golden/functions.pt)."""
     import os
@@ -239,3 +273,174 @@ def test_clip_variance_of_nearly_singular_covariances(be):
     gper = ((DV.cpu().double() - vd.grad).abs().amax(dim=(1, 2)) / vd.grad.abs().amax(dim=(1, 2)))
     assert float(gper.max()) < 5e-3, float(gper.max())
     print("fp32 evaluation of the reference's closed form: %d of %d matrices give a zero / non-finite sigma_min" % (broken, m))
+
+
+# ---- transfer-time normalisation (transfer.py:31-62): mnk_kp_hull_area, mnk_kp_normalize --------------------------------------
+def _hull_sets():
+    """point sets on a 1/64 grid in [-1, 1]^2: every coordinate difference is a multiple of 1/64 below 2^8 / 64 and every cross
+    product a multiple of 1/4096 below 2^15 / 4096 -- exact in fp32, so fp32 and fp64 decide every turn alike"""
+    g = torch.Generator().manual_seed(21)
+
+    def rnd(k, lo=-64, hi=64):
+        return (torch.randint(lo, hi + 1, (k, 2), generator=g).double() / 64).tolist()
+
+    sets = {"k3": [[-0.5, -0.25], [0.75, 0.125], [0.0, 0.875]], "k10": rnd(10), "k32": rnd(32)}
+    dup = rnd(10)
+    dup[7] = list(min(dup))                                   # the left-most point (a hull vertex) twice
+    dup[9] = list(dup[4])
+    sets["k10-two-duplicates"] = dup
+    inner = rnd(6, -56, 56)                                   # strictly inside the square [-1, 1]^2
+    sets["k10-four-collinear-on-an-edge"] = inner[:2] + [[0.25, -1.0]] + inner[2:4] + [[1.0, -1.0], [-1.0, -1.0]] + inner[4:] + \
+        [[-0.5, -1.0]]
+    sets["k10-three-share-the-least-x"] = [[-1.0, 0.5]] + inner[:3] + [[-1.0, -0.5]] + inner[3:] + [[-1.0, 0.0]] + [[1.0, 0.25]]
+    sets["k10-all-but-three-interior"] = [[0.0, 1.0]] + [[x, y - 0.25] for x, y in rnd(7, -16, 16)] + [[1.0, -1.0], [-1.0, -1.0]]
+    return sets
+
+
+HULL_SETS = _hull_sets()
+
+
+def _monotone_chain(points, dtype):
+    """Andrew's monotone chain (collinear and repeated points dropped) and the shoelace sum, every operation in `dtype`:
+    -> (hull vertices in order, area, sum over the hull's edges of |x_p y_q| + |x_q y_p|)"""
+    import numpy as np
+    pts = [(dtype(x), dtype(y)) for x, y in sorted((float(x), float(y)) for x, y in points)]
+
+    def cross(o, a, b):
+        return (a[0] - o[0]) * (b[1] - o[1]) - (a[1] - o[1]) * (b[0] - o[0])
+
+    def half(seq):
+        h = []
+        for p in seq:
+            while len(h) >= 2 and cross(h[-2], h[-1], p) <= 0:
+                h.pop()
+            h.append(p)
+        return h[:-1]
+
+    hull = half(pts) + half(pts[::-1])
+    a2, mag = dtype(0), 0.0
+    for p, q in zip(hull, hull[1:] + hull[:1]):
+        a2 = a2 + (p[0] * q[1] - q[0] * p[1])
+        mag += abs(float(p[0]) * float(q[1])) + abs(float(q[0]) * float(p[1]))
+    return [(float(x), float(y)) for x, y in hull], float(np.abs(a2)) / 2, mag
+
+
+def test_hull_restatement_keeps_its_hull_in_fp32():
+    """the committed point sets: the fp32 and the fp64 run of the restatement pick the same hull vertices (so the kernel's fp32
+    turns cannot differ from the reference's for a reason of rounding), and the sets hold the cases they are named for"""
+    import numpy as np
+    for name, pts in HULL_SETS.items():
+        h64, a64, _ = _monotone_chain(pts, np.float64)
+        h32, a32, _ = _monotone_chain(pts, np.float32)
+        assert h32 == h64 and a32 == a64, name
+        assert all(abs(v * 64) == int(abs(v * 64)) and abs(v) <= 1 for p in pts for v in p), name
+        assert len(h64) >= 3 and a64 > 0, name
+    assert _monotone_chain(HULL_SETS["k3"], np.float64)[1] == 0.5 * abs(1.25 * 1.125 - 0.375 * 0.5)
+    assert _monotone_chain(HULL_SETS["k10-all-but-three-interior"], np.float64)[:2] == ([(-1.0, -1.0), (1.0, -1.0), (0.0, 1.0)], 2.0)
+    assert len(set(map(tuple, HULL_SETS["k10-two-duplicates"]))) == 8
+    h = _monotone_chain(HULL_SETS["k10-four-collinear-on-an-edge"], np.float64)[0]
+    assert (-1.0, -1.0) in h and (1.0, -1.0) in h and (0.25, -1.0) not in h and (-0.5, -1.0) not in h
+    h = _monotone_chain(HULL_SETS["k10-three-share-the-least-x"], np.float64)[0]
+    assert (-1.0, 0.5) in h and (-1.0, -0.5) in h and (-1.0, 0.0) not in h
+
+
+@pytest.mark.parametrize("name", list(HULL_SETS))
+def test_hull_area(be, name):
+    """mnk_kp_hull_area (scipy.spatial.ConvexHull(points).volume of transfer.py:34-35) against the fp64 monotone chain +
+    shoelace restatement above.  Bound: the rounding of the shoelace terms, 4 * 2^-24 * sum over the hull's edges of
+    |x_p y_q| + |x_q y_p|."""
+    import numpy as np
+    from mnk._lib import MnkError
+    pts = HULL_SETS[name]
+    _, want, mag = _monotone_chain(pts, np.float64)
+    P, area = be.t(torch.tensor(pts, dtype=torch.float32)), be.empty(1)
+    be.call("mnk_kp_hull_area", P, len(pts), area)
+    be.sync()
+    got = float(area.cpu()[0])
+    print("%s: area %.9g, fp64 %.9g, bound %.3g" % (name, got, want, 4 * 2.0 ** -24 * mag))
+    assert abs(got - want) <= 4 * 2.0 ** -24 * mag
+    for bad in (2, 33):
+        with pytest.raises(MnkError):
+            be.call("mnk_kp_hull_area", be.zeros(bad, 2), bad, area)
+
+
+# source covariances whose transfer has a non-positive eigenvalue (make_symetric_matrix, transfer.py:17-28): the two of
+# dropin_worker.scenario_transfer_batched -- indefinite with a mixed term; diagonal with p < r --, diagonal with p > r (the other
+# eigenvector branch of the kernel's closed form), both eigenvalues negative
+KP_REPAIRS = [[[0.02, 0.05], [0.05, 0.01]], [[-0.03, 0.0], [0.0, 0.02]], [[0.02, 0.0], [0.0, -0.03]], [[-0.02, 0.005], [0.005, -0.01]]]
+
+
+def _normalize_inputs(B, D, K):
+    g = torch.Generator().manual_seed(100 * B + 10 * D + K)
+    mv = torch.rand(B, D, K, 2, generator=g) * 1.8 - 0.9
+    ma = torch.rand(B, 1, K, 2, generator=g) * 1.8 - 0.9
+    ma[0, 0, 0] = torch.tensor([1.25, -1.5])                  # outside [-1, 1] whatever the frame: clip_mean acts (also for D = 1)
+    a = torch.randn(B, 1, K, 2, 2, generator=g)
+    base = 0.02 * (a @ a.transpose(-1, -2) + torch.eye(2))
+    p = torch.randn(B, D, K, 2, 2, generator=g)
+    vv = base + 0.004 * (p @ p.transpose(-1, -2))
+    a = torch.randn(B, 1, K, 2, 2, generator=g)
+    va = 0.02 * (a @ a.transpose(-1, -2) + torch.eye(2))
+    slots = []
+    for j, m in enumerate(KP_REPAIRS[:B * K]):
+        b, k = j % B, j // B
+        va[b, 0, k] = torch.tensor(m)
+        if j > 0:     # the driving covariances multiples of the identity: the transferred one is 2^e * the source's, exactly
+            vv[b, :, k] = torch.eye(2) * torch.tensor([0.03125, 0.0625, 0.015625, 0.03125, 0.125])[:D].view(D, 1, 1)
+        slots.append((b, k))
+    return mv, vv, ma, va, slots
+
+
+@pytest.mark.parametrize("B,D,K", [(1, 1, 3), (2, 3, 4), (3, 5, 10)])
+def test_kp_normalize_direct(be, B, D, K):
+    """mnk_kp_normalize against the fp64 restatement of transfer.py:31-62 (_kp_restate, the one test_inference's transfer test
+    uses), 2e-6 absolute as there: every flag combination mnk.engine.normalize_kp can send (clip_mean only with move_location,
+    at least one of move_location / adapt_variance) x hull areas given / NULL x var_out given / NULL (means only; not with
+    adapt_variance).  Inputs: means that leave [-1, 1], and transferred covariances with a non-positive eigenvalue (KP_REPAIRS)
+    next to ordinary ones."""
+    import math
+    from mnk._lib import MnkError
+    from _kp_restate import normalize_kp_fp64
+    mv, vv, ma, va, slots = _normalize_inputs(B, D, K)
+    d = [t.double() for t in (mv, vv, ma, va)]
+    area_a, area_v = torch.tensor([1.21]), torch.tensor([0.49])
+    mult = math.sqrt(float(area_a)) / math.sqrt(float(area_v))                          # of the fp32 numbers the kernel reads
+    # from the fp64 side: the inputs hold what they are meant to
+    for m in (mult, 1.0):
+        assert float(normalize_kp_fp64(*d, m, True, False, False)[0].abs().max()) > 1.2
+    prod = torch.matmul(torch.matmul(d[1], torch.linalg.inv(d[1][:, 0:1])), d[3])
+    ev = torch.linalg.eigvalsh((prod + prod.transpose(-1, -2)) / 2)                     # ascending
+    assert float(ev.abs().min()) > 1e-4                       # no eigenvalue that fp32 rounding could carry across 0
+    for j, (b, k) in enumerate(slots):
+        assert bool((ev[b, :, k, 0] <= 0).all()), ("no repair here", j)
+        assert bool((ev[b, :, k, 1] <= 0).all()) == (j == 3), j
+        if j in (1, 2):
+            assert float(prod[b, :, k, 0, 1].abs().max()) == 0 and bool((prod[b, :, k, 0, 0] > prod[b, :, k, 1, 1]).all()) == (j == 2)
+    assert B * K == len(slots) or int((ev[..., 0] > 0).sum()) > 0                       # ... next to ones that need no repair
+    MV, VV, MA, VA = be.t(mv), be.t(vv.reshape(B, D, K, 4)), be.t(ma), be.t(va.reshape(B, 1, K, 4))
+    AA, AV = be.t(area_a), be.t(area_v)
+    worst = [0.0, 0.0]
+    for ml, cm, av in ((1, 0, 0), (1, 1, 0), (1, 0, 1), (1, 1, 1), (0, 0, 1)):
+        for areas in (True, False):
+            for with_var in (True, False):
+                if av and not with_var:
+                    continue
+                want_m, want_v = normalize_kp_fp64(*d, mult if areas else 1.0, bool(ml), bool(cm), bool(av))
+                MO, VO = be.empty(B, D, K, 2), (be.empty(B, D, K, 4) if with_var else None)
+                be.call("mnk_kp_normalize", MV, VV, MA, VA, B, D, K, AA if areas else None, AV if areas else None, ml, cm, av, MO, VO)
+                be.sync()
+                worst[0] = max(worst[0], maxerr(MO.cpu(), want_m))
+                assert maxerr(MO.cpu(), want_m) < 2e-6, (ml, cm, av, areas, with_var)
+                if with_var:
+                    worst[1] = max(worst[1], maxerr(VO.cpu().view(B, D, K, 2, 2), want_v))
+                    assert maxerr(VO.cpu().view(B, D, K, 2, 2), want_v) < 2e-6, (ml, cm, av, areas, with_var)
+                    if not av:
+                        assert torch.equal(VO.cpu(), vv.reshape(B, D, K, 4))
+    print("worst |mean - fp64| %.2e, |var - fp64| %.2e" % tuple(worst))
+    MO, VO = be.empty(B, D, K, 2), be.empty(B, D, K, 4)
+    with pytest.raises(MnkError):                             # one area without the other
+        be.call("mnk_kp_normalize", MV, VV, MA, VA, B, D, K, AA, None, 1, 0, 0, MO, VO)
+    with pytest.raises(MnkError):                             # adapt_variance without an output for it
+        be.call("mnk_kp_normalize", MV, VV, MA, VA, B, D, K, None, None, 1, 0, 1, MO, None)
+    be.sync()
+    assert torch.isnan(MO.cpu()).all() and torch.isnan(VO.cpu()).all()

@@ -193,3 +193,114 @@ def test_feature_matching_tap_adds_the_next_blocks_gradient(be):
     (act3 * be.t(nxt)).sum().backward()
     be.sync()
     assert torch.equal(A3.grad.cpu(), nxt)
+
+
+# ---- the entry points called directly on guard-banded buffers (the autograd functions above allocate from torch's pool) -------
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 200, 841])
+@pytest.mark.parametrize("b", [1, 3])
+def test_gan_terms_direct(be, b, n):
+    """mnk_gan_terms_fwd / _bwd against fp64 means of (1 - s_f)^2 and (1 - s_r)^2 + s_f^2 and their gradients.  A lane of the
+    forward kernel strides by 64: n = 64 +- 1 sits on that stride, 841 (a 29 x 29 score map) gives a lane 14 terms.  Backward
+    with the generator term alone, the discriminator term alone and both; the absent one is NULL.  Tolerances: those of
+    test_gan_terms_match_the_loss_module."""
+    from mnk._lib import MnkError
+    g = torch.Generator().manual_seed(60 + n)
+    wg, wd = 1.5, 0.75
+    score = torch.randn(2 * b, n, generator=g)
+    gg, gd = torch.randn(b, generator=g), torch.randn(b, generator=g)
+    s64 = score.double().requires_grad_(True)
+    ref_g = wg * ((1 - s64[:b]) ** 2).mean(1)
+    ref_d = wd * ((1 - s64[b:]) ** 2 + s64[:b] ** 2).mean(1)
+    S, GG, GD = be.t(score), be.t(gg), be.t(gd)
+    gen, disc = be.empty(b), be.empty(b)
+    be.call("mnk_gan_terms_fwd", S, n, b, wg, wd, gen, disc)
+    be.sync()
+    eg, ed = relerr(gen.cpu(), ref_g.detach()), relerr(disc.cpu(), ref_d.detach())
+    print("b %d n %d: relerr gen %.2e disc %.2e" % (b, n, eg, ed))
+    assert eg < 2e-6 and ed < 2e-6
+    for use_g, use_d in ((True, False), (False, True), (True, True)):
+        s64.grad = None
+        ref = (ref_g * gg.double()).sum() * float(use_g) + (ref_d * gd.double()).sum() * float(use_d)
+        ref.backward(retain_graph=True)
+        DS = be.empty(2 * b, n)
+        be.call("mnk_gan_terms_bwd", S, n, b, wg, wd, GG if use_g else None, GD if use_d else None, DS)
+        be.sync()
+        assert maxerr(DS.cpu(), s64.grad) < 1e-6 * (1 + float(s64.grad.abs().max())), (use_g, use_d)
+        if not use_d:
+            assert torch.all(DS.cpu()[b:] == 0)              # the real frames' scores are in the discriminator term only
+    DS = be.empty(2 * b, n)
+    with pytest.raises(MnkError):
+        be.call("mnk_gan_terms_bwd", S, n, b, wg, wd, None, None, DS)
+    be.sync()
+    assert torch.isnan(DS.cpu()).all()
+
+
+def _off_by_one_float(be, x):
+    """x as a view that starts one float past a 256-byte boundary (the header promises only `n contiguous floats`)"""
+    buf = be.empty(x.numel() + 1)
+    view = buf[1:].view(x.shape)
+    view.copy_(x)
+    assert view.data_ptr() % 16 == 4
+    return view
+
+
+@pytest.mark.parametrize("n", [1, 5, 1023, 1024, 1025, 12289])
+@pytest.mark.parametrize("b", [1, 4])
+def test_l1_mean_direct(be, b, n):
+    """mnk_l1_mean_fwd / _bwd against fp64 weight * mean |a - b| per sample and torch.abs' gradient (0 at ties), on inputs
+    that are not 16-byte aligned.  The forward block strides by 1024.  Backward with da alone, db alone and both: the present
+    output has the same bits in all three.  Tolerances: those of test_l1_mean_and_its_autograd_function."""
+    g = torch.Generator().manual_seed(70 + n)
+    weight = 7.0
+    a, bb = torch.randn(b, n, generator=g), torch.randn(b, n, generator=g)
+    ties = sorted({0, n // 2, n - 1, min(n - 1, 1024)})      # exact ties, one of them past the block's first stride
+    for i in range(b):
+        bb[i, ties] = a[i, ties]
+    gout = torch.randn(b, generator=g)
+    a64, b64 = a.double().requires_grad_(True), bb.double().requires_grad_(True)
+    ref = weight * (a64 - b64).abs().mean(1)
+    (ref * gout.double()).sum().backward()
+    A, B, G = _off_by_one_float(be, a), _off_by_one_float(be, bb), be.t(gout)
+    out = be.empty(b)
+    be.call("mnk_l1_mean_fwd", A, B, n, b, weight, out)
+    be.sync()
+    err = relerr(out.cpu(), ref.detach())
+    print("b %d n %d: relerr %.2e" % (b, n, err))
+    assert err < 2e-6
+    DA, DB, DA1, DB1 = (_off_by_one_float(be, torch.full((b, n), float("nan"))) for _ in range(4))
+    be.call("mnk_l1_mean_bwd", A, B, n, b, weight, G, DA, DB)
+    be.call("mnk_l1_mean_bwd", A, B, n, b, weight, G, DA1, None)
+    be.call("mnk_l1_mean_bwd", A, B, n, b, weight, G, None, DB1)
+    be.sync()
+    da, db = DA.cpu(), DB.cpu()
+    assert maxerr(da, a64.grad) < 1e-6 * (1 + float(a64.grad.abs().max()))
+    assert maxerr(db, b64.grad) < 1e-6 * (1 + float(b64.grad.abs().max()))
+    assert torch.all(da[:, ties] == 0) and torch.all(db[:, ties] == 0)          # +0.0 or -0.0
+    assert torch.equal(DA1.cpu().view(torch.int32), da.view(torch.int32))
+    assert torch.equal(DB1.cpu().view(torch.int32), db.view(torch.int32))
+
+
+@pytest.mark.parametrize("shape", [(3, 5, 7, 6), (2, 64, 30, 30), (1, 13, 4, 4), (4, 256, 2, 2)])
+def test_pair_l1_bwd_add_direct(be, shape):
+    """mnk_pair_l1_bwd_add at test_pair_l1_forward_backward's shapes: without an addend the bits of mnk_pair_l1_bwd, with one
+    those of (mnk_pair_l1_bwd's output + addend) formed in fp32 on the host -- one rounding per element either way.  `a`, `g`
+    and `addend` are const arguments: the guarded call checks that they are unchanged."""
+    b, c, h, w = shape
+    g = torch.Generator().manual_seed(9)
+    fake = torch.randn(b, c, h, w, generator=g)
+    real = torch.randn(b, c, h, w, generator=g)
+    real[0, 0, 0, :2] = fake[0, 0, 0, :2]                    # exact ties
+    add = to_nhwc(torch.randn(2 * b, c, h, w, generator=g))  # an act's gradient: pad channels 0
+    weight, ld = 10.0, ceil4(c)
+    A, G, ADD = be.t(to_nhwc(torch.cat([fake, real], 0))), be.t(torch.randn(b, generator=g)), be.t(add)
+    D0, D1, D2 = (be.empty(2 * b, h, w, ld) for _ in range(3))
+    be.call("mnk_pair_l1_bwd", A, ld, h * w, c, b, weight, G, D0)
+    be.call("mnk_pair_l1_bwd_add", A, ld, h * w, c, b, weight, G, None, D1)
+    be.call("mnk_pair_l1_bwd_add", A, ld, h * w, c, b, weight, G, ADD, D2)
+    be.sync()
+    d0 = D0.cpu()
+    assert not torch.isnan(d0).any()
+    assert torch.equal(D1.cpu().view(torch.int32), d0.view(torch.int32))
+    want = d0 + add
+    assert torch.equal(D2.cpu().view(torch.int32), want.view(torch.int32))
+    assert torch.all(D2.cpu()[..., c:] == 0)
