@@ -249,12 +249,24 @@ size_t mnk_conv3x3_stats_floats(int N, int H, int W, int C0, int C1, int Cout);
  * without the flag.  Composes with the three flags above.  No backward kernel differentiates this form, so a non-NULL
  * `stats_partial` (a training request) is rejected as an invalid argument and nothing is launched. */
 #define MNK_CONV_BF16 8
+/* (= 16, forward AND data gradient) opt-in mixed-precision TRAINING products: the same one-pass form as MNK_CONV_BF16 -- both
+ * operands rounded to nearest-even bf16 in the loaders, exact products, fp32 accumulation -- but allowed together with
+ * `stats_partial` and with the BatchNorm-backward hand-over of the *_bnstats entries: the statistics are fp32 column sums of the
+ * fp32 accumulators.  A data gradient is this same kernel on dy and the data-gradient pack: mnk_conv3x3_fwd / mnk_conv2d_fwd take
+ * the flag there, and the entries that have no `flags` argument have an _ex form that takes 0 or MNK_CONV_BF16_TRAIN
+ * (mnk_conv3x3_up_dgrad_ex, mnk_conv3x3_dgrad_bnstats_ex, mnk_conv3x3_up_dgrad_bnstats_ex; the old names are the _ex forms with
+ * 0).  Tile, split, workspace and statistics sizes are those of the unflagged call; a launch that would walk position-major,
+ * tap-skipping rows without the flag walks frame-major with it (those rows are fp32 only).  MNK_CONV_BF16 keeps its meaning:
+ * with it -- alone or together with this flag -- a non-NULL `stats_partial` is still rejected.  Bits above 16 are invalid.
+ * Weights, gradients and activations stay fp32 in memory. */
+#define MNK_CONV_BF16_TRAIN 16
 int mnk_conv3x3_splits(int N, int H, int W, int C0, int C1, int Cout);
 int mnk_conv3x3_up_splits(int N, int H, int W, int C0, int C1, int Cout);
 int mnk_conv3x3_fwd(const float* x0, int ld0, int C0, const float* x1, int ld1, int C1, int flags, const float* wp,
                     const float* bias, const float* residual, int ld_res, float* y, int ld_y, int N, int H, int W,
                     int Cout, float* ws, size_t ws_floats, float* stats_partial, void* stream);
-/* dw[co][c_start+ci][ky][kx] = sum_pixels dy[p][co] * x[p+tap][ci]; x is one source (C channels) */
+/* dw[co][c_start+ci][ky][kx] = sum_pixels dy[p][co] * x[p+tap][ci]; x is one source (C channels)
+ * `flags`: MNK_CONV_UPSAMPLED | MNK_CONV_CLEAN_PADS | MNK_WGRAD_DEFER | MNK_WGRAD_BF16 (below) */
 size_t mnk_conv3x3_wgrad_workspace_floats(int N, int H, int W, int C, int Cout);
 int mnk_conv3x3_wgrad(const float* x, int ld_x, int C, int flags, const float* dy, int ld_dy, int Cout, float* dw,
                       int Cin_total, int c_start, int N, int H, int W, float* ws, size_t ws_floats, void* stream);
@@ -277,10 +289,12 @@ size_t mnk_conv3x3_up_workspace_floats(int N, int H, int W, int C0, int C1, int 
 size_t mnk_conv3x3_up_stats_floats(int N, int H, int W, int C0, int C1, int Cout);
 int mnk_conv3x3_up_fwd(const float* x0, int ld0, int C0, const float* x1, int ld1, int C1, int flags, const float* wp_up,
                        const float* bias, float* y, int ld_y, int N, int H, int W, int Cout, float* ws, size_t ws_floats,
-                       float* stats_partial, void* stream);     /* flags: 0, MNK_CONV_DEFER_SPLITK and / or MNK_CONV_BF16 */
+                       float* stats_partial, void* stream);     /* flags: MNK_CONV_DEFER_SPLITK | MNK_CONV_BF16 | MNK_CONV_BF16_TRAIN */
 size_t mnk_conv3x3_up_dgrad_workspace_floats(int N, int H, int W, int Cout, int C);
 int mnk_conv3x3_up_dgrad(const float* dy, int ld_dy, int Cout, const float* wp_up_dgrad, float* dx, int ld_dx, int N, int H,
                          int W, int C, float* ws, size_t ws_floats, void* stream);
+int mnk_conv3x3_up_dgrad_ex(const float* dy, int ld_dy, int Cout, const float* wp_up_dgrad, float* dx, int ld_dx, int N, int H,
+                            int W, int C, float* ws, size_t ws_floats, int flags, void* stream);  /* flags: 0 or MNK_CONV_BF16_TRAIN */
 /* Data-gradient launches that ALSO leave the backward statistics of the BatchNorm (+ activation) layer whose output they
  * differentiate (round 4; sync_batchnorm/batchnorm.py:48-78 backward through modules/util.py:56-62,81-87): dx of the
  * convolution IS dz of the norm layer in front when that layer's output has no other consumer, and the GEMM epilogue holds the
@@ -294,11 +308,21 @@ int mnk_conv3x3_dgrad_bnstats(const float* dy, int ld_dy, int Cout, const float*
                               float* dx, int ld_dx, int N, int H, int W, int C, float* ws, size_t ws_floats, float* stats_partial,
                               const float* bn_y, int ld_bny, const float* bn_mean, const float* bn_invstd, const float* bn_scale,
                               const float* bn_beta, float slope, void* stream);
+/* (the _ex forms: `flags` = 0 or MNK_CONV_BF16_TRAIN; dx is the plain flagged data gradient bit for bit, the statistics are
+ * fp32 sums over its fp32 accumulators) */
+int mnk_conv3x3_dgrad_bnstats_ex(const float* dy, int ld_dy, int Cout, const float* wp_dgrad, const float* residual, int ld_res,
+                                 float* dx, int ld_dx, int N, int H, int W, int C, float* ws, size_t ws_floats, float* stats_partial,
+                                 const float* bn_y, int ld_bny, const float* bn_mean, const float* bn_invstd, const float* bn_scale,
+                                 const float* bn_beta, float slope, int flags, void* stream);
 size_t mnk_conv3x3_up_dgrad_stats_floats(int N, int H, int W, int Cout, int C);
 int mnk_conv3x3_up_dgrad_bnstats(const float* dy, int ld_dy, int Cout, const float* wp_up_dgrad, float* dx, int ld_dx, int N, int H,
                                  int W, int C, float* ws, size_t ws_floats, float* stats_partial, const float* bn_y, int ld_bny,
                                  const float* bn_mean, const float* bn_invstd, const float* bn_scale, const float* bn_beta,
                                  float slope, void* stream);
+int mnk_conv3x3_up_dgrad_bnstats_ex(const float* dy, int ld_dy, int Cout, const float* wp_up_dgrad, float* dx, int ld_dx, int N,
+                                    int H, int W, int C, float* ws, size_t ws_floats, float* stats_partial, const float* bn_y,
+                                    int ld_bny, const float* bn_mean, const float* bn_invstd, const float* bn_scale,
+                                    const float* bn_beta, float slope, int flags, void* stream);
 
 /* ---- general K x K form of the same kernels (stride 1).  Used for the discriminator's nn.Conv3d((1,4,4)) without
  * padding (modules/discriminator.py:17-18; SURVEY.md section 8f row 1, the first "next" component): forward
@@ -331,6 +355,16 @@ int mnk_conv2d_wgrad(const float* x, int ld_x, int C, int flags, int Hi, int Wi,
  * parameter gradient.  Descriptor table in device memory, sorted by block_begin; layer i owns
  * mnk_wgrad_reduce_blocks(splits, Cout, C) blocks from block_begin; total_blocks = their sum.  Deterministic order. */
 #define MNK_WGRAD_DEFER 4
+/* (= 8; `flags` of mnk_conv2d_wgrad, mnk_conv3x3_wgrad and MnkWgradJob) opt-in mixed-precision TRAINING products of the weight
+ * gradient, the counterpart of MNK_CONV_BF16_TRAIN.  Where the form selection lands on the tap-major or the sub-pixel form (the
+ * wide layers: where the multiply-adds are), the launch runs the one-plane bf16 form of that kernel: its transposing loader rounds
+ * x and dy to nearest-even bf16, the products are exact, accumulation, split partials and their reduction are fp32 -- one
+ * v_mfma_f32_32x32x16_bf16 per tile pair and 16 pixels.  The nine-tap (narrow layers), LDS-halo and gather forms ACCEPT the flag
+ * and keep fp32 products: the bits of the unflagged call.  The plan is that of the unflagged call in every respect -- form,
+ * variant, splits, layout, part_floats, workspace -- so every query answers for both.  With the flag set the launch does not
+ * consult the "wgrad_bf16x3" tuning value.  Grouped launches: all tap-major jobs of one table must agree on the bit
+ * (mnk_wgrad_grouped_build rejects a mixed table as an invalid argument).  Bits above 8 are invalid. */
+#define MNK_WGRAD_BF16 8
 typedef struct MnkWgradPlan {
     int layout;          /* 0: tap-major partials [split][tap][Cout][C]; 1: parameter-major [split][Cout][C * ntaps];
                           * 2: tap-major with the 16 pseudo taps of the sub-pixel form (mnk_conv2d_wgrad_plan2) */
@@ -392,7 +426,7 @@ typedef struct MnkWgradJob {
     const float* dy;
     float* part;
     size_t part_floats;                      /* out (plan) */
-    int ld_x, C, flags, ld_dy, Cout;         /* flags: MNK_CONV_UPSAMPLED | MNK_CONV_CLEAN_PADS */
+    int ld_x, C, flags, ld_dy, Cout;         /* flags: MNK_CONV_UPSAMPLED | MNK_CONV_CLEAN_PADS | MNK_WGRAD_BF16 */
     int N, Ho, Wo, Hi, Wi, kh, kw, pad;
     int variant, splits;                     /* out (plan) */
     int layout;                              /* out (plan): MnkWgradPlan::layout of the partials (0, or 2: sub-pixel form) */

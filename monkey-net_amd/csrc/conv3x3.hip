@@ -1897,12 +1897,14 @@ static int conv2d_fwd_impl(const float* x0, int ld0, int C0, const float* x1, in
                            int kw, int pad, int stride, int phases, const float* wp, const float* bias, const float* residual,
                            int ld_res, float* y, int ld_y, int N, int Ho, int Wo, int Cout, float* ws, size_t ws_floats,
                            float* stats_partial, void* stream, const BnBwdSrc* bnb = nullptr) {
-    MNK_REQUIRE(flags >= 0 && flags <= 15);
+    MNK_REQUIRE(flags >= 0 && flags <= 31);
     const int ups = flags & MNK_CONV_UPSAMPLED, clean = (flags & MNK_CONV_CLEAN_PADS) ? 1 : 0;
-    // MNK_CONV_BF16: the one-pass bf16 products (GM = 2) -- a property of this launch; tile and split are those of the fp32 plan.
-    // Inference only: the column sums of the epilogue are a training request, and no backward kernel differentiates this form
-    const bool one_pass = (flags & MNK_CONV_BF16) != 0;
-    MNK_REQUIRE(!one_pass || (!stats_partial && !bnb));
+    // MNK_CONV_BF16 / MNK_CONV_BF16_TRAIN: the one-pass bf16 products (GM = 2) -- a property of this launch; tile and split are
+    // those of the fp32 plan.  MNK_CONV_BF16 is the inference request: the column sums of the epilogue are a training request and
+    // stay refused with it.  MNK_CONV_BF16_TRAIN is the training request (mixed precision: the data- and weight-gradient launches
+    // of the layer round the same way): the same products, with the fp32 statistics / BatchNorm-backward epilogues behind them
+    const bool one_pass = (flags & (MNK_CONV_BF16 | MNK_CONV_BF16_TRAIN)) != 0;
+    MNK_REQUIRE(!(flags & MNK_CONV_BF16) || (!stats_partial && !bnb));
     // MNK_CONV_DEFER_SPLITK: a split-K launch leaves its partials in `ws` ([split][phase][M][ldw], bias not added) and the
     // caller sums them (mnk_bn_small_fwd does, together with the normalisation that follows)
     const bool defer_splitk = (flags & MNK_CONV_DEFER_SPLITK) != 0;
@@ -2094,7 +2096,7 @@ size_t mnk_conv3x3_up_stats_floats(int N, int H, int W, int C0, int C1, int Cout
 int mnk_conv3x3_up_fwd(const float* x0, int ld0, int C0, const float* x1, int ld1, int C1, int flags, const float* wp_up,
                        const float* bias, float* y, int ld_y, int N, int H, int W, int Cout, float* ws, size_t ws_floats,
                        float* stats_partial, void* stream) {
-    MNK_REQUIRE((flags & ~(MNK_CONV_DEFER_SPLITK | MNK_CONV_BF16)) == 0);
+    MNK_REQUIRE((flags & ~(MNK_CONV_DEFER_SPLITK | MNK_CONV_BF16 | MNK_CONV_BF16_TRAIN)) == 0);
     return conv2d_fwd_impl(x0, ld0, C0, x1, ld1, C1, MNK_CONV_CLEAN_PADS | flags, H, W, 2, 2, 1, 1, 4, wp_up, bias, nullptr, 0, y,
                            ld_y, N, H, W, Cout, ws, ws_floats, stats_partial, stream);
 }
@@ -2105,10 +2107,16 @@ int mnk_conv3x3_up_splits(int N, int H, int W, int C0, int C1, int Cout) { retur
 size_t mnk_conv3x3_up_dgrad_workspace_floats(int N, int H, int W, int Cout, int C) {
     return plan_launch(16, 1, N, H, W, Cout, 0, C).ws_floats;
 }
+// the data-gradient entries without a `flags` argument have an _ex form that takes one: 0 or MNK_CONV_BF16_TRAIN
+int mnk_conv3x3_up_dgrad_ex(const float* dy, int ld_dy, int Cout, const float* wp_up_dgrad, float* dx, int ld_dx, int N, int H,
+                            int W, int C, float* ws, size_t ws_floats, int flags, void* stream) {
+    MNK_REQUIRE((flags & ~MNK_CONV_BF16_TRAIN) == 0);
+    return conv2d_fwd_impl(dy, ld_dy, Cout, nullptr, 0, 0, MNK_CONV_CLEAN_PADS | flags, 2 * H, 2 * W, 4, 4, 1, 2, 1, wp_up_dgrad,
+                           nullptr, nullptr, 0, dx, ld_dx, N, H, W, C, ws, ws_floats, nullptr, stream);
+}
 int mnk_conv3x3_up_dgrad(const float* dy, int ld_dy, int Cout, const float* wp_up_dgrad, float* dx, int ld_dx, int N, int H,
                          int W, int C, float* ws, size_t ws_floats, void* stream) {
-    return conv2d_fwd_impl(dy, ld_dy, Cout, nullptr, 0, 0, MNK_CONV_CLEAN_PADS, 2 * H, 2 * W, 4, 4, 1, 2, 1, wp_up_dgrad, nullptr,
-                           nullptr, 0, dx, ld_dx, N, H, W, C, ws, ws_floats, nullptr, stream);
+    return mnk_conv3x3_up_dgrad_ex(dy, ld_dy, Cout, wp_up_dgrad, dx, ld_dx, N, H, W, C, ws, ws_floats, 0, stream);
 }
 
 // ---- data-gradient launches that also leave the backward statistics of the BatchNorm layer in front (round 4) ------------------
@@ -2118,24 +2126,40 @@ static BnBwdSrc bnb_of(const float* bn_y, int ld_bny, const float* mean, const f
     b.y = bn_y, b.ld = ld_bny, b.mean = mean, b.invstd = invstd, b.scale = scale, b.beta = beta, b.slope = slope;
     return b;
 }
+int mnk_conv3x3_dgrad_bnstats_ex(const float* dy, int ld_dy, int Cout, const float* wp_dgrad, const float* residual, int ld_res,
+                                 float* dx, int ld_dx, int N, int H, int W, int C, float* ws, size_t ws_floats, float* stats_partial,
+                                 const float* bn_y, int ld_bny, const float* bn_mean, const float* bn_invstd, const float* bn_scale,
+                                 const float* bn_beta, float slope, int flags, void* stream) {
+    MNK_REQUIRE((flags & ~MNK_CONV_BF16_TRAIN) == 0);
+    const BnBwdSrc b = bnb_of(bn_y, ld_bny, bn_mean, bn_invstd, bn_scale, bn_beta, slope);
+    return conv2d_fwd_impl(dy, ld_dy, Cout, nullptr, 0, 0, MNK_CONV_CLEAN_PADS | flags, H, W, 3, 3, 1, 1, 1, wp_dgrad, nullptr,
+                           residual, ld_res, dx, ld_dx, N, H, W, C, ws, ws_floats, stats_partial, stream, &b);
+}
 int mnk_conv3x3_dgrad_bnstats(const float* dy, int ld_dy, int Cout, const float* wp_dgrad, const float* residual, int ld_res,
                               float* dx, int ld_dx, int N, int H, int W, int C, float* ws, size_t ws_floats, float* stats_partial,
                               const float* bn_y, int ld_bny, const float* bn_mean, const float* bn_invstd, const float* bn_scale,
                               const float* bn_beta, float slope, void* stream) {
-    const BnBwdSrc b = bnb_of(bn_y, ld_bny, bn_mean, bn_invstd, bn_scale, bn_beta, slope);
-    return conv2d_fwd_impl(dy, ld_dy, Cout, nullptr, 0, 0, MNK_CONV_CLEAN_PADS, H, W, 3, 3, 1, 1, 1, wp_dgrad, nullptr, residual,
-                           ld_res, dx, ld_dx, N, H, W, C, ws, ws_floats, stats_partial, stream, &b);
+    return mnk_conv3x3_dgrad_bnstats_ex(dy, ld_dy, Cout, wp_dgrad, residual, ld_res, dx, ld_dx, N, H, W, C, ws, ws_floats,
+                                        stats_partial, bn_y, ld_bny, bn_mean, bn_invstd, bn_scale, bn_beta, slope, 0, stream);
 }
 size_t mnk_conv3x3_up_dgrad_stats_floats(int N, int H, int W, int Cout, int C) {
     return plan_launch(16, 1, N, H, W, Cout, 0, C).stats_floats;
+}
+int mnk_conv3x3_up_dgrad_bnstats_ex(const float* dy, int ld_dy, int Cout, const float* wp_up_dgrad, float* dx, int ld_dx, int N,
+                                    int H, int W, int C, float* ws, size_t ws_floats, float* stats_partial, const float* bn_y,
+                                    int ld_bny, const float* bn_mean, const float* bn_invstd, const float* bn_scale,
+                                    const float* bn_beta, float slope, int flags, void* stream) {
+    MNK_REQUIRE((flags & ~MNK_CONV_BF16_TRAIN) == 0);
+    const BnBwdSrc b = bnb_of(bn_y, ld_bny, bn_mean, bn_invstd, bn_scale, bn_beta, slope);
+    return conv2d_fwd_impl(dy, ld_dy, Cout, nullptr, 0, 0, MNK_CONV_CLEAN_PADS | flags, 2 * H, 2 * W, 4, 4, 1, 2, 1, wp_up_dgrad,
+                           nullptr, nullptr, 0, dx, ld_dx, N, H, W, C, ws, ws_floats, stats_partial, stream, &b);
 }
 int mnk_conv3x3_up_dgrad_bnstats(const float* dy, int ld_dy, int Cout, const float* wp_up_dgrad, float* dx, int ld_dx, int N, int H,
                                  int W, int C, float* ws, size_t ws_floats, float* stats_partial, const float* bn_y, int ld_bny,
                                  const float* bn_mean, const float* bn_invstd, const float* bn_scale, const float* bn_beta,
                                  float slope, void* stream) {
-    const BnBwdSrc b = bnb_of(bn_y, ld_bny, bn_mean, bn_invstd, bn_scale, bn_beta, slope);
-    return conv2d_fwd_impl(dy, ld_dy, Cout, nullptr, 0, 0, MNK_CONV_CLEAN_PADS, 2 * H, 2 * W, 4, 4, 1, 2, 1, wp_up_dgrad, nullptr,
-                           nullptr, 0, dx, ld_dx, N, H, W, C, ws, ws_floats, stats_partial, stream, &b);
+    return mnk_conv3x3_up_dgrad_bnstats_ex(dy, ld_dy, Cout, wp_up_dgrad, dx, ld_dx, N, H, W, C, ws, ws_floats, stats_partial, bn_y,
+                                           ld_bny, bn_mean, bn_invstd, bn_scale, bn_beta, slope, 0, stream);
 }
 
 // ---- 3x3 / pad 1 forms (the hot path's nn.Conv3d (1,3,3)) ------------------------------------------------------------

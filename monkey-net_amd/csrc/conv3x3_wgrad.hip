@@ -821,14 +821,18 @@ __device__ __forceinline__ void wgrad_tap_body(const WgradTapArgs& a, const int 
 // plane and channel.  LDS image per plane: 16-byte chunks [k group of 8][channel], chunk(kg, m) = kg * BMP + m + (m >> 4) (one pad
 // chunk per 16 channels: conflict-free b128 fragment reads, 2-way on the writes).  Threads [0, BM) load dy, [BM, BM + BN) load x.
 // Generic addressing only (magic-number divisions, clamps, masks, the compact K of small maps): the split dominates the loader.
-template <int BM, int BN, int WM, int WN, bool SUBPIX>
+// NPL = 3: the exact three-way split ("wgrad_bf16x3", six MFMAs per tile pair).  NPL = 1: the one-plane form of MNK_WGRAD_BF16 --
+// the loader rounds each operand to nearest-even bf16 (mnk_round_bf16x4, the first plane of the split), one MFMA per tile pair;
+// the same chunk layout, per plane.
+template <int BM, int BN, int WM, int WN, bool SUBPIX, int NPL>
 __device__ __forceinline__ void wgrad_tap_body_h(const WgradTapArgs& a, const int bx, const int by, const int split) {
+    static_assert(NPL == 1 || NPL == 3, "one rounded plane or the three-way split");
     static_assert(WM * WN == 4, "4 waves per block");
     static_assert(BM + BN <= 256, "one loader thread per (pixel group, channel quad) of both operands");
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
     constexpr int BMP = BM + BM / 16, BNP = BN + BN / 16;
-    __shared__ __attribute__((aligned(16))) uint4 Ah[2][3][2 * BMP];
-    __shared__ __attribute__((aligned(16))) uint4 Bh[2][3][2 * BNP];
+    __shared__ __attribute__((aligned(16))) uint4 Ah[2][NPL][2 * BMP];
+    __shared__ __attribute__((aligned(16))) uint4 Bh[2][NPL][2 * BNP];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int wm = wave / WN, wn = wave % WN;
     const int co0 = bx * BM;
@@ -930,13 +934,18 @@ __device__ __forceinline__ void wgrad_tap_body_h(const WgradTapArgs& a, const in
         const int pstride = is_a ? 2 * BMP : 2 * BNP, kstride = is_a ? BMP : BNP;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            uint2 p0, p1, p2;
-            mnk_split3(make_float4(m[0][e], m[1][e], m[2][e], m[3][e]), p0, p1, p2);
             const int row = rowbase + e;
             const int chunk = kg * kstride + row + (row >> 4);
-            reinterpret_cast<uint2*>(planes + chunk)[half] = p0;
-            reinterpret_cast<uint2*>(planes + pstride + chunk)[half] = p1;
-            reinterpret_cast<uint2*>(planes + 2 * pstride + chunk)[half] = p2;
+            const float4 k4 = make_float4(m[0][e], m[1][e], m[2][e], m[3][e]);
+            if constexpr (NPL == 1) {
+                reinterpret_cast<uint2*>(planes + chunk)[half] = mnk_round_bf16x4(k4);
+            } else {
+                uint2 p0, p1, p2;
+                mnk_split3(k4, p0, p1, p2);
+                reinterpret_cast<uint2*>(planes + chunk)[half] = p0;
+                reinterpret_cast<uint2*>(planes + pstride + chunk)[half] = p1;
+                reinterpret_cast<uint2*>(planes + 2 * pstride + chunk)[half] = p2;
+            }
         }
     };
 
@@ -952,9 +961,9 @@ __device__ __forceinline__ void wgrad_tap_body_h(const WgradTapArgs& a, const in
                 for (int r = 0; r < 16; ++r) acc[q][i][j][r] = 0.f;
     const int fi = lane & 31, fk = lane >> 5;
     auto mfma_step = [&](int buf) __attribute__((always_inline)) {
-        mnk_bf16x8 ha[3][TM], hb[3][TN];
+        mnk_bf16x8 ha[NPL][TM], hb[NPL][TN];
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl) {
+        for (int pl = 0; pl < NPL; ++pl) {
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
                 const int row = wm * (32 * TM) + 32 * i + fi;
@@ -971,12 +980,18 @@ __device__ __forceinline__ void wgrad_tap_body_h(const WgradTapArgs& a, const in
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 constexpr int Q = NACC - 1;
-                acc[0][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ha[1][i], hb[1][j], acc[0][i][j], 0, 0, 0);
-                acc[Q][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ha[2][i], hb[0][j], acc[Q][i][j], 0, 0, 0);
-                acc[0][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ha[0][i], hb[2][j], acc[0][i][j], 0, 0, 0);
-                acc[Q][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ha[1][i], hb[0][j], acc[Q][i][j], 0, 0, 0);
-                acc[0][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ha[0][i], hb[1][j], acc[0][i][j], 0, 0, 0);
-                acc[Q][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ha[0][i], hb[0][j], acc[Q][i][j], 0, 0, 0);
+                if constexpr (NPL == 1) {
+                    // one MFMA per tile pair; a lone tile alternates two accumulators so that consecutive K steps do not chain
+                    if (Q && (buf & 1)) acc[Q][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ha[0][i], hb[0][j], acc[Q][i][j], 0, 0, 0);
+                    else acc[0][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ha[0][i], hb[0][j], acc[0][i][j], 0, 0, 0);
+                } else {
+                    acc[0][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ha[1][i], hb[1][j], acc[0][i][j], 0, 0, 0);
+                    acc[Q][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ha[2][i], hb[0][j], acc[Q][i][j], 0, 0, 0);
+                    acc[0][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ha[0][i], hb[2][j], acc[0][i][j], 0, 0, 0);
+                    acc[Q][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ha[1][i], hb[0][j], acc[Q][i][j], 0, 0, 0);
+                    acc[0][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ha[0][i], hb[1][j], acc[0][i][j], 0, 0, 0);
+                    acc[Q][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ha[0][i], hb[0][j], acc[Q][i][j], 0, 0, 0);
+                }
             }
     };
 
@@ -1034,11 +1049,11 @@ __device__ __forceinline__ void wgrad_tap_body_h(const WgradTapArgs& a, const in
         emit(FalseTag{});
 }
 
-template <int BM, int BN, int WM, int WN, bool SUBPIX>
+template <int BM, int BN, int WM, int WN, bool SUBPIX, int NPL = 3>
 __global__ void __launch_bounds__(256, 2) conv3x3_wgrad_tap_h_kernel(WgradTapArgs a) {
     int bx, by;
     xcd_tile(a.xcd, bx, by);
-    wgrad_tap_body_h<BM, BN, WM, WN, SUBPIX>(a, bx, by, (int)blockIdx.z);
+    wgrad_tap_body_h<BM, BN, WM, WN, SUBPIX, NPL>(a, bx, by, (int)blockIdx.z);
 }
 
 template <int BM, int BN, int WM, int WN, int MODE>
@@ -1081,7 +1096,7 @@ __global__ void __launch_bounds__(256, 3) conv3x3_wgrad_tap_grouped_kernel(const
     wgrad_tap_body<BM, BN, WM, WN, MODE>(a, bx, by, split);
 }
 
-template <int BM, int BN, int WM, int WN, bool SUBPIX>
+template <int BM, int BN, int WM, int WN, bool SUBPIX, int NPL = 3>
 __global__ void __launch_bounds__(256, 2) conv3x3_wgrad_tap_grouped_h_kernel(const TapJobRec* __restrict__ recs, int n) {
     __shared__ int sh_idx;
     int b = blockIdx.x;
@@ -1096,7 +1111,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_wgrad_tap_grouped_h_kernel(con
     const int gm = rp->gm, gnt = rp->gnt;
     const int bx = local % gm, rest = local / gm;
     const int by = rest % gnt, split = rest / gnt;
-    wgrad_tap_body_h<BM, BN, WM, WN, SUBPIX>(a, bx, by, split);
+    wgrad_tap_body_h<BM, BN, WM, WN, SUBPIX, NPL>(a, bx, by, split);
 }
 
 // the nine-tap 16x16 kernel for MANY narrow layers in one launch (the eight 45 -> 45 convolutions of the refinement stack:
@@ -2089,9 +2104,13 @@ static void fill_n16_args(WgradN16Args& g, const MnkWgradJob& j, const NPlan& np
 }
 
 // the tap-major kernel of a tile (tap_tile_id) and loader mode; bf16x3: one generic-loader form per tile (plain / sub-pixel)
+// one_plane (MNK_WGRAD_BF16): the one-plane form of the same kernel; it wins over the tuning value
 template <int BM, int BN, int WM, int WN>
-static void launch_tap_tile(int mode, dim3 grid, hipStream_t st, const WgradTapArgs& g) {
-    if (g_wgrad_bf16x3) {
+static void launch_tap_tile(int mode, dim3 grid, hipStream_t st, const WgradTapArgs& g, bool one_plane) {
+    if (one_plane) {
+        if (mode == 3) hipLaunchKernelGGL((conv3x3_wgrad_tap_h_kernel<BM, BN, WM, WN, true, 1>), grid, dim3(256), 0, st, g);
+        else hipLaunchKernelGGL((conv3x3_wgrad_tap_h_kernel<BM, BN, WM, WN, false, 1>), grid, dim3(256), 0, st, g);
+    } else if (g_wgrad_bf16x3) {
         if (mode == 3) hipLaunchKernelGGL((conv3x3_wgrad_tap_h_kernel<BM, BN, WM, WN, true>), grid, dim3(256), 0, st, g);
         else hipLaunchKernelGGL((conv3x3_wgrad_tap_h_kernel<BM, BN, WM, WN, false>), grid, dim3(256), 0, st, g);
     } else if (mode == 1) hipLaunchKernelGGL((conv3x3_wgrad_tap_kernel<BM, BN, WM, WN, 1>), grid, dim3(256), 0, st, g);
@@ -2100,8 +2119,11 @@ static void launch_tap_tile(int mode, dim3 grid, hipStream_t st, const WgradTapA
     else hipLaunchKernelGGL((conv3x3_wgrad_tap_kernel<BM, BN, WM, WN, 0>), grid, dim3(256), 0, st, g);
 }
 template <int BM, int BN, int WM, int WN>
-static void launch_tap_tile_grouped(int mode, int blocks, hipStream_t st, const TapJobRec* rv, int cnt) {
-    if (g_wgrad_bf16x3) {
+static void launch_tap_tile_grouped(int mode, int blocks, hipStream_t st, const TapJobRec* rv, int cnt, bool one_plane) {
+    if (one_plane) {
+        if (mode == 3) hipLaunchKernelGGL((conv3x3_wgrad_tap_grouped_h_kernel<BM, BN, WM, WN, true, 1>), dim3(blocks), dim3(256), 0, st, rv, cnt);
+        else hipLaunchKernelGGL((conv3x3_wgrad_tap_grouped_h_kernel<BM, BN, WM, WN, false, 1>), dim3(blocks), dim3(256), 0, st, rv, cnt);
+    } else if (g_wgrad_bf16x3) {
         if (mode == 3) hipLaunchKernelGGL((conv3x3_wgrad_tap_grouped_h_kernel<BM, BN, WM, WN, true>), dim3(blocks), dim3(256), 0, st, rv, cnt);
         else hipLaunchKernelGGL((conv3x3_wgrad_tap_grouped_h_kernel<BM, BN, WM, WN, false>), dim3(blocks), dim3(256), 0, st, rv, cnt);
     } else if (mode == 1) hipLaunchKernelGGL((conv3x3_wgrad_tap_grouped_kernel<BM, BN, WM, WN, 1>), dim3(blocks), dim3(256), 0, st, rv, cnt);
@@ -2169,8 +2191,10 @@ size_t mnk_conv3x3_up_wgrad_workspace_floats(int N, int Ho, int Wo, int C, int C
 int mnk_conv2d_wgrad(const float* x, int ld_x, int C, int flags, int Hi, int Wi, int kh, int kw, int pad, const float* dy,
                      int ld_dy, int Cout, float* dw, int Cin_total, int c_start, int N, int Ho, int Wo, float* ws,
                      size_t ws_floats, void* stream) {
-    MNK_REQUIRE(flags >= 0 && flags <= 7);
+    MNK_REQUIRE(flags >= 0 && flags <= 15);
     const int ups = flags & MNK_CONV_UPSAMPLED;
+    // MNK_WGRAD_BF16: the tap-major forms run their one-plane bf16 kernel; the plan (and every other form) does not look at it
+    const bool one_plane = (flags & MNK_WGRAD_BF16) != 0;
     // MNK_WGRAD_DEFER: leave the split partials in `ws` (layout / size: mnk_conv2d_wgrad_plan) and skip the reduction --
     // the caller reduces the partials of many layers in one launch (mnk_wgrad_reduce_multi)
     const bool defer = (flags & MNK_WGRAD_DEFER) != 0;
@@ -2205,10 +2229,10 @@ int mnk_conv2d_wgrad(const float* x, int ld_x, int C, int flags, int Hi, int Wi,
                                                    : subpix ? 2.0 * (double)s.M * Cout * 16.0 * C : -1.0);
             const dim3 grid(s.t.gm, s.t.gn * s.ntaps, s.splits);
             switch (tap_tile_id(s.t)) {
-                case 0: launch_tap_tile<128, 128, 2, 2>(s.mode, grid, st, g); break;
-                case 1: launch_tap_tile<128, 64, 2, 2>(s.mode, grid, st, g); break;
-                case 2: launch_tap_tile<64, 128, 1, 4>(s.mode, grid, st, g); break;
-                default: launch_tap_tile<32, 128, 1, 4>(s.mode, grid, st, g); break;
+                case 0: launch_tap_tile<128, 128, 2, 2>(s.mode, grid, st, g, one_plane); break;
+                case 1: launch_tap_tile<128, 64, 2, 2>(s.mode, grid, st, g, one_plane); break;
+                case 2: launch_tap_tile<64, 128, 1, 4>(s.mode, grid, st, g, one_plane); break;
+                default: launch_tap_tile<32, 128, 1, 4>(s.mode, grid, st, g, one_plane); break;
             }
             break;
         }
@@ -2307,8 +2331,12 @@ int mnk_wgrad_grouped_build(const MnkWgradJob* jobs, int n, void* host_table, si
     hd->magic = 0x4d4e4b47;
     hd->n = n;
     hd->nvariants = 25;
-    hd->reserved = 0;
-    int k = 0;
+    hd->reserved = 0;       // 1: the tap-major jobs run the one-plane bf16 form (MNK_WGRAD_BF16) -- all of them or none
+    int k = 0, tap_jobs = 0, tap_bf16 = 0;
+    for (int i = 0; i < n; ++i)
+        if (jobs[i].variant >= 0 && jobs[i].variant < 16) ++tap_jobs, tap_bf16 += (jobs[i].flags & MNK_WGRAD_BF16) ? 1 : 0;
+    MNK_REQUIRE(tap_bf16 == 0 || tap_bf16 == tap_jobs);
+    hd->reserved = tap_bf16 ? 1 : 0;
     for (int v = 0; v < 25; ++v) {
         hd->first[v] = k;
         int blocks = 0;
@@ -2350,7 +2378,8 @@ int mnk_wgrad_grouped_build(const MnkWgradJob* jobs, int n, void* host_table, si
 int mnk_wgrad_grouped_launch(const void* device_table, const void* host_table, void* stream) {
     MNK_REQUIRE(device_table && host_table);
     const GroupedHeader* hd = (const GroupedHeader*)host_table;
-    MNK_REQUIRE(hd->magic == 0x4d4e4b47 && hd->n > 0);
+    MNK_REQUIRE(hd->magic == 0x4d4e4b47 && hd->n > 0 && (hd->reserved == 0 || hd->reserved == 1));
+    const bool one_plane = hd->reserved == 1;
     const TapJobRec* hrecs = (const TapJobRec*)((const char*)host_table + sizeof(GroupedHeader));
     const TapJobRec* drecs = (const TapJobRec*)((const char*)device_table + sizeof(GroupedHeader));
     hipStream_t st = (hipStream_t)stream;
@@ -2368,10 +2397,10 @@ int mnk_wgrad_grouped_launch(const void* device_table, const void* host_table, v
         const TapJobRec* rv = drecs + hd->first[v];
         const int mode = v % 4;
         switch (v / 4) {
-            case 0: launch_tap_tile_grouped<128, 128, 2, 2>(mode, blocks, st, rv, cnt); break;
-            case 1: launch_tap_tile_grouped<128, 64, 2, 2>(mode, blocks, st, rv, cnt); break;
-            case 2: launch_tap_tile_grouped<64, 128, 1, 4>(mode, blocks, st, rv, cnt); break;
-            default: launch_tap_tile_grouped<32, 128, 1, 4>(mode, blocks, st, rv, cnt); break;
+            case 0: launch_tap_tile_grouped<128, 128, 2, 2>(mode, blocks, st, rv, cnt, one_plane); break;
+            case 1: launch_tap_tile_grouped<128, 64, 2, 2>(mode, blocks, st, rv, cnt, one_plane); break;
+            case 2: launch_tap_tile_grouped<64, 128, 1, 4>(mode, blocks, st, rv, cnt, one_plane); break;
+            default: launch_tap_tile_grouped<32, 128, 1, 4>(mode, blocks, st, rv, cnt, one_plane); break;
         }
     }
     for (int v = 16; v < 25; ++v) {

@@ -155,8 +155,10 @@ class TrainPairRunner:
         for o in self.owners.values():
             o.begin_pass()
         mops.clear_dz_stats()
-        kp_joined = joined_kp(self.kp, x)
-        generated = self.gen(x["source"], **split_kp(kp_joined, tp["detach_kp_generator"]))
+        # MNK_TRAIN_PRECISION: the convolution nodes record the precision here; phases B and C follow what they recorded
+        with mops.training_precision(train_precision()):
+            kp_joined = joined_kp(self.kp, x)
+            generated = self.gen(x["source"], **split_kp(kp_joined, tp["detach_kp_generator"]))
         fake = generated["video_prediction"]
         fake_leaf = fake.detach().requires_grad_(True)
         names = list(kp_joined.keys())
@@ -319,7 +321,7 @@ class TrainPairRunner:
         self.epoch += 1
         dev = self.device
         if self.use_graph:
-            key = tuple(x["source"].shape)
+            key = tuple(x["source"].shape) + (train_precision(),)      # a captured program keeps the precision it was built with
             prog = self.programs.get(key)
             if prog is not None and (prog.reg_version != mops.pack_registry_version() or prog.ptrs != self._tensor_ptrs()):
                 prog = None              # packed-weight buffers were re-created / a storage was swapped: addresses are in the graphs
@@ -406,6 +408,13 @@ class TrainPairRunner:
                 self._phase_c(cur, grads)
         if which == "d" and not isinstance(cur, _Program):
             self.cur = None              # the iteration's autograd graph may go
+
+
+def train_precision():
+    """the precision of the training iterations TrainPairRunner serves: an enclosing ops.training_precision scope where it is not
+    fp32, else MNK_TRAIN_PRECISION"""
+    scope = mops.current_training_precision()
+    return scope if scope != "fp32" else mops.check_precision(knobs.get("MNK_TRAIN_PRECISION"))
 
 
 _BROKEN = []

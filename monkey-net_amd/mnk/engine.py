@@ -135,8 +135,12 @@ class TrainStep:
     """One iteration of train.py:110-136 on this rank's shard, with gradients averaged over ranks (RCCL) before
     every optimiser step."""
 
-    def __init__(self, generator, discriminator, kp_detector, train_params, fused_adam=None, use_graph=False):
-        """fused_adam: None / True -- mnk.optim.MnkAdam (one hand-written launch per optimiser step that also emits the
+    def __init__(self, generator, discriminator, kp_detector, train_params, fused_adam=None, use_graph=False, precision="fp32"):
+        """precision: "fp32", or "bf16" -- the iteration (and, with use_graph, its warm-up and capture) runs inside
+        ops.training_precision(precision): the 3x3 convolutions of generator and key-point detector round the operands of their
+        forward, data-gradient and weight-gradient GEMMs to bf16, everything else stays fp32.  A captured
+        iteration keeps the precision it was built with.
+        fused_adam: None / True -- mnk.optim.MnkAdam (one hand-written launch per optimiser step that also emits the
         packed conv weights of the next iteration; weight-gradient split reductions of all layers in one launch; the flat
         gradient buffer is what the ranks all-reduce); False -- stock torch.optim.Adam (non-fused) + per-layer
         reductions + bucketed GradAverager, the structure of round 1, kept as the comparison path of the tests."""
@@ -144,6 +148,7 @@ class TrainStep:
         self.tp = train_params
         lr = train_params['lr']
         self.use_graph = bool(use_graph)
+        self.precision = mops.check_precision(precision)
         self.mnk_adam = True if fused_adam is None else bool(fused_adam)
         self._graph = None                    # the captured iteration: a list of hipGraphs and host calls between them
         self._segment = None                  # (graph being captured, pool) while _capture runs
@@ -202,9 +207,11 @@ class TrainStep:
         if mdist._P2P["handle"] is not None and self._iterations % 32 == 0:
             mdist.check_p2p()                 # a peer that an exchange gave up on: raise, do not train on poisoned statistics
         if not self.use_graph:
-            return self._eager_step(x)
+            with mops.training_precision(self.precision):
+                return self._eager_step(x)
         if self._graph is None:
-            self._capture(x)
+            with mops.training_precision(self.precision):
+                self._capture(x)
         if self.mnk_adam:
             if self._weights_touched:         # e.g. a checkpoint was loaded between two replays
                 mops.repack_registered()

@@ -39,6 +39,10 @@ KNOBS = {
                                    "(mnk.ops.inference_precision; INTEGRATION.md).  Part of the captured program's key: changing the "
                                    "variable re-captures instead of replaying the other form.  An enclosing bf16 "
                                    "inference_precision scope takes precedence; the wrapper's eager fall-backs use the same value"),
+    "MNK_TRAIN_PRECISION": ("fp32", "the training iteration that mnk.dropin.TrainPairRunner serves behind the reference's own train.py: "
+                                    "fp32, or bf16 = the 3x3 convolutions run forward, data gradient and weight gradient on "
+                                    "bf16-rounded operands with fp32 accumulation (mnk.ops.training_precision; INTEGRATION.md 2d).  Part "
+                                    "of the captured program's key: changing the variable captures a program of its own"),
     "MNK_ADOPT_ADAM": ("1", "a stock torch.optim.Adam over a network whose gradients the drop-in runner keeps in one flat buffer is "
                             "stepped by mnk_adam_multi on the optimiser's own state tensors (mnk.optim.AdoptedAdam); 0: the stock step"),
     "MNK_NATIVE_PREDICTION": ("0", "1: `import modules.prediction_module` (prediction.py:10) resolves to mnk.predictor, the key-point "

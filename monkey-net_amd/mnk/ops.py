@@ -595,12 +595,15 @@ def _gemm_launch(form, x0, c0, x1, c1, wp, bias, residual, n, h, w, cout, flags=
         flags |= 4                       # MNK_CONV_DEFER_SPLITK
     # (plain positional calls: this is the host-bound evaluation loops' path)
     ld1, ldr = x1.shape[-1] if x1 is not None else 0, residual.shape[-1] if residual is not None else 0
+    # MNK_CONV_BF16_TRAIN on an entry that has no `flags` argument: its _ex form (the plain names are the _ex forms with 0)
+    ex = ("_ex", (flags & 16,)) if flags & 16 else ("", ())
     if bn is not None and st is not None:
         tail = (_p(ws), nws, _p(st), _p(bn.y), bn.y.shape[-1], _p(bn.mean), _p(bn.invstd), _p(bn.scale), _p(bn.beta), float(bn.slope))
         if form == "3x3":
-            _call(f.bn_launch, x0, _p(x0), x0.shape[-1], c0, _p(wp), _p(residual), ldr, _p(y), y.shape[-1], n, h, w, cout, *tail)
+            _call(f.bn_launch + ex[0], x0, _p(x0), x0.shape[-1], c0, _p(wp), _p(residual), ldr, _p(y), y.shape[-1], n, h, w, cout,
+                  *tail, *ex[1])
         else:
-            _call(f.bn_launch, x0, _p(x0), x0.shape[-1], c0, _p(wp), _p(y), y.shape[-1], n, h, w, cout, *tail)
+            _call(f.bn_launch + ex[0], x0, _p(x0), x0.shape[-1], c0, _p(wp), _p(y), y.shape[-1], n, h, w, cout, *tail, *ex[1])
     elif form == "3x3":
         _call(f.launch, x0, _p(x0), x0.shape[-1], c0, _p(x1), ld1, c1, flags, _p(wp), _p(bias), _p(residual), ldr, _p(y), y.shape[-1],
               n, h, w, cout, _p(ws), nws, _p(st))
@@ -608,7 +611,7 @@ def _gemm_launch(form, x0, c0, x1, c1, wp, bias, residual, n, h, w, cout, flags=
         _call(f.launch, x0, _p(x0), x0.shape[-1], c0, _p(x1), ld1, c1, flags, _p(wp), _p(bias), _p(y), y.shape[-1], n, h, w, cout,
               _p(ws), nws, _p(st))
     elif form == "up_dgrad":
-        _call(f.launch, x0, _p(x0), x0.shape[-1], c0, _p(wp), _p(y), y.shape[-1], n, h, w, cout, _p(ws), nws)
+        _call(f.launch + ex[0], x0, _p(x0), x0.shape[-1], c0, _p(wp), _p(y), y.shape[-1], n, h, w, cout, _p(ws), nws, *ex[1])
     else:
         _call(f.launch, x0, _p(x0), x0.shape[-1], c0, _p(x1), ld1, c1, flags, *kxk, _p(wp), _p(bias), _p(residual), ldr, _p(y),
               y.shape[-1], n, h, w, cout, _p(ws), nws, _p(st))
@@ -665,7 +668,43 @@ def current_precision():
     return _PRECISION[0]
 
 
-def _conv_launch(x0, c0, x1, c1, ups, wp, bias, residual, n, h, w, cout, want_stats=False, up=False, eval_defer=False):
+# ---- opt-in bf16 (mixed-precision) training ---------------------------------------------------------------------------------------
+# the precision of the three GEMMs of a 3x3 / sub-pixel convolution NODE -- forward (MNK_CONV_BF16_TRAIN, training statistics
+# included), data gradient (the same flag) and weight gradient (MNK_WGRAD_BF16) -- that is called with gradients enabled.  The
+# operands are rounded to nearest-even bf16 in the loaders, products are exact, accumulation is fp32; weights, gradients, activations
+# and optimiser state stay fp32 in memory, and so does every other layer: the discriminator's 4x4 convolutions and first-block
+# kernels, 1x1 and grouped 1x1 convolutions, norm layers, warp, embedding, soft-argmax, losses, Adam.
+_TRAIN_PRECISION = ["fp32"]
+
+
+class training_precision:
+    """Context manager: inside `with training_precision("bf16"):` every 3x3 and sub-pixel convolution called with gradients
+    enabled runs its forward products in one bf16 pass and records that on its autograd node; the node's data- and weight-gradient
+    GEMMs follow the RECORDED value, also when backward() runs after the scope was left.  A node is bf16 in all three GEMMs or in
+    none: bf16_excluded(cin, cout) decides at forward time.  Calls under torch.no_grad() are not touched (fp32 unless an
+    inference_precision scope says otherwise), and inference_precision keeps its own semantics inside this scope.  Outside any
+    scope the precision is fp32; the previous value is restored on exit, also after an exception.  One value per process, like
+    inference_precision."""
+
+    def __init__(self, precision):
+        self.precision = check_precision(precision)
+
+    def __enter__(self):
+        self.previous = _TRAIN_PRECISION[0]
+        _TRAIN_PRECISION[0] = self.precision
+        return self
+
+    def __exit__(self, *exc):
+        _TRAIN_PRECISION[0] = self.previous
+        return False
+
+
+def current_training_precision():
+    return _TRAIN_PRECISION[0]
+
+
+def _conv_launch(x0, c0, x1, c1, ups, wp, bias, residual, n, h, w, cout, want_stats=False, up=False, eval_defer=False,
+                 train_bf16=False):
     """One conv launch.  With want_stats the BatchNorm sums of the output come out of the conv epilogue (finished by a
     tiny second-stage kernel) instead of a separate pass over y; returns (y, sums or None).  up: `wp` holds the
     sub-pixel packs of an up-sampled convolution and (h, w) is the up-sampled size.  eval_defer: conv3x3(eval_bn=True)."""
@@ -681,7 +720,9 @@ def _conv_launch(x0, c0, x1, c1, ups, wp, bias, residual, n, h, w, cout, want_st
     # pad channels (tests/test_modules.py::test_pad_channels_are_written pins that), so the fast 3x3 loader applies
     form, hq, wq, flags = ("up", h // 2, w // 2, 0) if up else ("3x3", h, w, int(ups) | 2)
     # MNK_CONV_BF16 (conv3x3 vouches for no_grad and an evaluation-mode norm layer).  Not for bf16_excluded layers: they stay fp32
-    if _PRECISION[0] == "bf16" and not bf16_excluded(c0 + c1, cout):
+    if train_bf16:
+        flags |= 16                          # MNK_CONV_BF16_TRAIN: the node's decision (Conv3x3Fn.forward), statistics allowed
+    elif _PRECISION[0] == "bf16" and not bf16_excluded(c0 + c1, cout):
         flags |= 8
     y, st = _gemm_launch(form, x0, c0, x1, c1, wp, bias, residual, n, hq, wq, cout, flags, want_stats and not small, small or evald)
     if small:
@@ -819,11 +860,15 @@ class Conv3x3Fn(_Fn):
     nearest x2 up-sampling (UpBlock3D, modules/util.py:83-85), plus bias and residual add (ResBlock3D :66-67)."""
 
     @staticmethod
-    def forward(ctx, x0, x1, weight, bias, residual, c0, c1, ups, want_stats, track, src_bn=None, eval_defer=False):
+    def forward(ctx, x0, x1, weight, bias, residual, c0, c1, ups, want_stats, track, src_bn=None, eval_defer=False,
+                train_bf16=False):
         """src_bn: (the _BnRecord of the norm layer whose output x0 is, or None; the same for x1), see _BN_OF.
-        eval_defer: conv3x3(eval_bn=True), see _conv_launch."""
+        eval_defer: conv3x3(eval_bn=True), see _conv_launch.  train_bf16: conv3x3 was called with gradients enabled inside
+        training_precision("bf16")."""
         _check_device(x0)
         cout = weight.shape[0]
+        # the node's precision, decided once: its three GEMMs are bf16 or none is
+        ctx.bf16 = bool(train_bf16) and not bf16_excluded(c0 + c1, cout)
         assert weight.shape[1] == c0 + c1 and weight.is_contiguous()
         n, hs, ws_, _ = x0.shape
         h, w = (hs * 2, ws_ * 2) if ups else (hs, ws_)
@@ -836,7 +881,7 @@ class Conv3x3Fn(_Fn):
             wp, ctx.wd = e.wp, list(e.wd)
         else:
             wp = _packed_fwd_weight(weight, cout, c0, c1, up)
-        y, sums = _conv_launch(x0, c0, x1, c1, ups, wp, bias, residual, n, h, w, cout, want_stats, up, eval_defer)
+        y, sums = _conv_launch(x0, c0, x1, c1, ups, wp, bias, residual, n, h, w, cout, want_stats, up, eval_defer, ctx.bf16)
         ctx.up = up
         ctx.src_bn = src_bn if track and src_bn is not None else (None, None)
         ctx.save_for_backward(x0, x1, weight)
@@ -857,7 +902,7 @@ class Conv3x3Fn(_Fn):
         x0, x1, weight = ctx.saved_tensors
         c0, c1, ups, cout, n, h, w, has_bias, has_res = ctx.meta
         if dy is None:                       # (materialize_grads is off) nothing flows into y
-            return (dskip if ctx.needs_input_grad[0] else None,) + (None,) * 11
+            return (dskip if ctx.needs_input_grad[0] else None,) + (None,) * 12
         if dskip is not None and not ctx.needs_input_grad[0]:
             dskip = None
         dy_in = dy
@@ -890,7 +935,7 @@ class Conv3x3Fn(_Fn):
                     rec = None
             if rec is not None and tuple(rec.y.shape) != (n, hd, wd, ceil4(cc)):
                 rec = None
-            dx, st = _gemm_launch(form, dy, cout, None, 0, wp, None, res, n, hd, wd, cc, 2, bn=rec)
+            dx, st = _gemm_launch(form, dy, cout, None, 0, wp, None, res, n, hd, wd, cc, 2 | (16 if ctx.bf16 else 0), bn=rec)
             if rec is not None and st is not None:
                 _DZ_STATS[dx.data_ptr()] = (dx, st, st.numel() // (2 * dx.shape[-1]), rec.y.data_ptr())
             if ups and not ctx.up:
@@ -904,10 +949,12 @@ class Conv3x3Fn(_Fn):
             # optimiser's flat buffer and the split reduction waits for the one launch that serves every layer
             owner = wgrad_sink_owner(weight)
             taken = [False, False]
+            # | 2: MNK_CONV_CLEAN_PADS (x and dy are acts of this module); | 8: MNK_WGRAD_BF16, the precision the forward recorded
+            wflags = int(ups) | 2 | (8 if ctx.bf16 else 0)
             if owner is not None:
                 for i, (src, cs, cc) in enumerate(((x0, 0, c0), (x1, c0, c1))):
                     if src is not None:
-                        taken[i] = owner.reducer.wgrad(weight, src, src.shape[-1], cc, int(ups) | 2, h, w, 3, 3, 1, dy,
+                        taken[i] = owner.reducer.wgrad(weight, src, src.shape[-1], cc, wflags, h, w, 3, 3, 1, dy,
                                                        ld_dy, cout, cin, cs, n, h, w)
             rest = [(src, cs, cc) for i, (src, cs, cc) in enumerate(((x0, 0, c0), (x1, c0, c1)))
                     if src is not None and not taken[i]]
@@ -917,8 +964,8 @@ class Conv3x3Fn(_Fn):
                 nws = _query("mnk_conv3x3_up_wgrad_workspace_floats" if ups else "mnk_conv3x3_wgrad_workspace_floats", n, h, w,
                              cc, cout)
                 ws = SCRATCH.get("ws", nws, dy) if nws else None
-                _call("mnk_conv3x3_wgrad", dy, _p(src), src.shape[-1], cc, int(ups) | 2, _p(dy), ld_dy, cout, _p(dw), cin,
-                      cs, n, h, w, _p(ws), nws)      # | 2: MNK_CONV_CLEAN_PADS (x and dy are acts of this module)
+                _call("mnk_conv3x3_wgrad", dy, _p(src), src.shape[-1], cc, wflags, _p(dy), ld_dy, cout, _p(dw), cin,
+                      cs, n, h, w, _p(ws), nws)
             if owner is not None and dw is not None:
                 owner.add_to_sink(weight, dw)        # a further contribution before the step (slow path)
                 dw = None
@@ -934,7 +981,7 @@ class Conv3x3Fn(_Fn):
         dres = dy if has_res and ctx.needs_input_grad[4] else None
         if dskip is not None:                # forms without a residual operand (up-sampled sources): one add
             grads[0] = grads[0] + dskip if grads[0] is not None else dskip
-        return grads[0], grads[1], dw, db, dres, None, None, None, None, None, None, None
+        return grads[0], grads[1], dw, db, dres, None, None, None, None, None, None, None, None
 
 
 class Conv3x3SkipFn(_Fn):
@@ -944,8 +991,10 @@ class Conv3x3SkipFn(_Fn):
     gradient in the epilogue of its data-gradient GEMM (the `residual` operand) -- no accumulation pass by autograd."""
 
     @staticmethod
-    def forward(ctx, x0, x1, weight, bias, residual, c0, c1, ups, want_stats, track, src_bn=None, eval_defer=False):
-        y, sums = Conv3x3Fn.forward(ctx, x0, x1, weight, bias, residual, c0, c1, ups, want_stats, track, src_bn, eval_defer)
+    def forward(ctx, x0, x1, weight, bias, residual, c0, c1, ups, want_stats, track, src_bn=None, eval_defer=False,
+                train_bf16=False):
+        y, sums = Conv3x3Fn.forward(ctx, x0, x1, weight, bias, residual, c0, c1, ups, want_stats, track, src_bn, eval_defer,
+                                    train_bf16)
         return y, sums, x0
 
     @staticmethod
@@ -971,7 +1020,9 @@ def conv3x3(x0, c0, weight, bias=None, x1=None, c1=0, ups=False, residual=None, 
     eval_defer = bool(eval_bn and not want_stats and residual is None and not torch.is_grad_enabled()
                       and knobs.form("EVAL_SPLIT_FUSED"))
     src_bn = (_bn_of(x0), _bn_of(x1)) if track else None     # the norm layers whose outputs the sources are (see _BN_OF)
-    args = (x0, x1, weight, bias, residual, c0, c1, bool(ups), bool(want_stats), track, src_bn, eval_defer)
+    # training_precision("bf16"): a call with gradients enabled; no_grad calls are left to inference_precision
+    train_bf16 = _TRAIN_PRECISION[0] == "bf16" and torch.is_grad_enabled()
+    args = (x0, x1, weight, bias, residual, c0, c1, bool(ups), bool(want_stats), track, src_bn, eval_defer, train_bf16)
     if skip and track and x0.requires_grad and knobs.form("SKIP_GRAD_FUSED"):
         y, sums, through = Conv3x3SkipFn.apply(*args)
         return y, (sums if want_stats else None), through

@@ -146,6 +146,8 @@ class DeferredReducer:
         if rec is None or rec["shape"] != shape:
             rec = self._record(key, weight, sink, shape, int(flags))
         if rec["grouped"]:
+            # the plan does not depend on MNK_WGRAD_BF16 (bit 3): the job carries the bit of THIS backward pass
+            rec["job"]["flags"][0] = (int(rec["job"]["flags"][0]) & ~8) | (int(flags) & 8)
             self.jobs.append((key, x, dy))                 # launched by flush(); the operands stay alive until then
             self.job_macs += float(n * ho * wo) * c * cout * kh * kw
             if self.bg_macs > 0 and self.job_macs >= self.bg_macs and x.is_cuda and not _capturing(x.device):
@@ -173,6 +175,14 @@ class DeferredReducer:
     def _launch_grouped(self, background=False):
         jobs, self.jobs = self.jobs, []
         self.job_macs = 0.0
+        # one table holds jobs of one precision (mnk_wgrad_grouped_build): layers that training_precision("bf16") leaves in fp32
+        # (ops.bf16_excluded, K x K convolutions) get a table of their own.  In fp32 there is one table, as ever
+        for bit in (0, 8):
+            some = [j for j in jobs if (int(self.recs[j[0]]["job"]["flags"][0]) & 8) == bit]
+            if some:
+                self._launch_grouped_table(some, background)
+
+    def _launch_grouped_table(self, jobs, background):
         lib = _lib.lib()
         dev = jobs[0][1].device
         arr = np.zeros(len(jobs), dtype=JOB)
