@@ -385,8 +385,22 @@ typedef struct MnkWgradReduceDesc {
     int layout, splits, ntaps, Cout, C, Cin_total, c_start;
     int accumulate;      /* 1: add to dw (a second contribution to the same parameter) */
     int block_begin;
-    int reserved;
+    int flags;           /* (the former `reserved`, 0 as before) bit 0, MNK_REDUCE_UP1X1, layout 2 only: the partials come from a
+                          * sub-pixel GEMM on a 1 x 1 low-resolution source (mnk_up1x1_dead_taps) -- the slices of its dead pseudo
+                          * taps were never written and are taken as +0.f without a load: the same sums, the same bits (such a
+                          * descriptor is summed by the flat or the tile map, whatever mnk_wgrad_reduce_map names) */
 } MnkWgradReduceDesc;
+#define MNK_REDUCE_UP1X1 1
+/* ---- up-sampled 3x3 convolutions on a 1 x 1 low-resolution source ("up1x1_dead_taps", default 1; 0: nothing below applies).
+ * Of the 16 pseudo taps of the sub-pixel forms only four per form ever meet the source there; the others read padding alone.
+ * mnk_up1x1_live_mask(dgrad): the live set as a bit mask over the forward / weight-gradient pseudo taps 4 * (2a + b) + 2u + v
+ * (dgrad = 0) or over the data-gradient taps 4 ty + tx (dgrad = 1) -- the one definition every kernel below uses.
+ * mnk_up1x1_dead_taps(N, Hs, Ws) = 1 when the sub-pixel weight-gradient GEMM of N frames of Hs x Ws LOW-resolution pixels makes
+ * no tiles for the dead pseudo taps and leaves their slices of the partials UNWRITTEN (Hs == Ws == 1, the tuning value on, the
+ * compact K form in use); 1 x W and H x 1 sources keep all 16.  Whoever reads such partials sets MNK_REDUCE_UP1X1 /
+ * MNK_ADAM_UP1X1; the single-layer entry's own reduction does. */
+int mnk_up1x1_live_mask(int dgrad);
+int mnk_up1x1_dead_taps(int N, int Hs, int Ws);
 int mnk_wgrad_reduce_blocks(int splits, int Cout, int C);
 /* the thread map mnk_wgrad_reduce_multi takes for such a layer under the live "wgrad_reduce_vec", GIVEN that `part` is 16-byte
  * aligned (the contract of the vector maps: a layer whose partials are not aligned is summed by the tile map, map 1, whatever
@@ -461,7 +475,12 @@ typedef struct MnkAdamDesc {
     float* wp_d1;
     int Cout, C0, C1, block_begin;
     int flags;      /* bit 0: an up-sampled convolution -- emit the packs of its sub-pixel forms (mnk_conv3x3_up_*);
-                       bit 1 / bit 2: gt0 / gt1 hold 16 pseudo taps of the sub-pixel weight-gradient form (folded here) */
+                       bit 1 / bit 2: gt0 / gt1 hold 16 pseudo taps of the sub-pixel weight-gradient form (folded here);
+                       bit 3 (MNK_ADAM_UP1X1, with bit 0): the layer runs on a 1 x 1 low-resolution source
+                       (mnk_up1x1_dead_taps): the dead pseudo-tap slices of gt0 / gt1 were never written and are taken as +0.f
+                       without a load, and the dead slices of the packs (forward tap4, data-gradient tap16) are not stored --
+                       they must hold finite values from an earlier full pack, and whoever needs them later (the same weight on
+                       a larger source) packs in full first */
     int ntaps;      /* 0 or 9: a 3x3 weight; else (<= 16) a K x K weight, ntaps = K * K: mnk_conv2d_pack_all's layouts are
                        emitted (flags and gt0 / gt1 must be 0) */
     /* optional: the gradient of source 0 / source 1 of a convolution weight taken straight from the tap-major partials of the
@@ -471,6 +490,7 @@ typedef struct MnkAdamDesc {
     const float* gt1;
     int gt_splits0, gt_splits1;
 } MnkAdamDesc;
+#define MNK_ADAM_UP1X1 8
 int mnk_adam_blocks(long n, int Cout, int C0, int C1, int packed);
 int mnk_adam_tick(float* hyper, void* stream);
 int mnk_adam_multi(const MnkAdamDesc* descs_device, int n, int total_blocks, const float* hyper, void* stream);

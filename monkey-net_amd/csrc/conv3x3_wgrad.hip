@@ -524,7 +524,9 @@ struct WgradTapArgs {
     // small maps (H * W <= wtap_compact, MODE 0 / 3): K runs over the pixels whose tap lies INSIDE the source only -- on a 2 x 2 map
     // a corner tap sees one pixel of four, an edge tap two (56 % of the (pixel, tap) pairs of a 3x3 pad-1 convolution are zeros
     // there, 31 % on 4 x 4, 16 % on 8 x 8; three quarters of the sub-pixel form's pseudo taps on a 1 x 1 source).  The range of a
-    // tap is cut into `nsplits` equal pieces.
+    // tap is cut into `nsplits` equal pieces.  compact == 2 (MODE 3 on a 1 x 1 source, up1x1_skips): the launch has tiles for the
+    // four LIVE pseudo taps only (pack_tile.h: up1x1_live_tap) -- the tile index along the taps counts phases, and the slices
+    // of the twelve dead pseudo taps of `part` are not written.
     int compact, nsplits;
     // MODE 3 -- sub-pixel form of an up-sampled 3x3 convolution: H, W, M are the LOW resolution; the 16 "taps" are
     // t = 4 * (2a + b) + (2u + v): dWeff[t] = sum_{n,i,j} dy[n, 2i+a, 2j+b] (x) x[n, i+a-1+u, j+b-1+v]  (4/9 of the multiply-adds of
@@ -549,14 +551,15 @@ __device__ __forceinline__ void wgrad_tap_body(const WgradTapArgs& a, const int 
     __shared__ __attribute__((aligned(16))) float Bs[2][BK][LDB];   // x-shifted [pixel][ci]
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int wm = wave / WN, wn = wave % WN;
+    constexpr bool SUBPIX = MODE == 3, FAST = MODE == 1 || MODE == 2;
     const int co0 = bx * BM;
-    const int tap = by / a.gn;
-    const int ci0 = (by - tap * a.gn) * BN;
+    const int tapi = by / a.gn;
+    const int ci0 = (by - tapi * a.gn) * BN;
+    const int tap = SUBPIX && a.compact == 2 ? up1x1_live_tap(tapi) : tapi;     // 1 x 1 source: tiles of the live pseudo taps only
     long p_begin = (long)split * a.pix_per_split;
     long p_end = p_begin + a.pix_per_split;
     if (p_end > a.M) p_end = a.M;
     const int Hs = a.ups ? a.Hi >> 1 : a.Hi, Ws = a.ups ? a.Wi >> 1 : a.Wi;
-    constexpr bool SUBPIX = MODE == 3, FAST = MODE == 1 || MODE == 2;
     const int ph_a = (tap >> 3) & 1, ph_b = (tap >> 2) & 1;                      // SUBPIX: output phase of this pseudo tap
     const int dyt = SUBPIX ? ph_a - 1 + ((tap >> 1) & 1) : tap / a.kw - a.pad;   // SUBPIX: low-resolution row / column offset
     const int dxt = SUBPIX ? ph_b - 1 + (tap & 1) : tap % a.kw - a.pad;
@@ -836,8 +839,9 @@ __device__ __forceinline__ void wgrad_tap_body_h(const WgradTapArgs& a, const in
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int wm = wave / WN, wn = wave % WN;
     const int co0 = bx * BM;
-    const int tap = by / a.gn;
-    const int ci0 = (by - tap * a.gn) * BN;
+    const int tapi = by / a.gn;
+    const int ci0 = (by - tapi * a.gn) * BN;
+    const int tap = SUBPIX && a.compact == 2 ? up1x1_live_tap(tapi) : tapi;     // (see wgrad_tap_body)
     long p_begin = (long)split * a.pix_per_split;
     long p_end = p_begin + a.pix_per_split;
     if (p_end > a.M) p_end = a.M;
@@ -1144,7 +1148,8 @@ __global__ void __launch_bounds__(256, 2) conv3x3_wgrad_n16_grouped_kernel(const
 __global__ void __launch_bounds__(256) conv3x3_wgrad_tap_reduce_kernel(const float* __restrict__ part, int splits,
                                                                        int ntaps, int Cout, int C,
                                                                        float* __restrict__ dw, long ld_out, int up) {
-    // up: `ntaps` = 16 pseudo taps of the sub-pixel form in `part`, folded into the 9 kernel taps of dw
+    // up: `ntaps` = 16 pseudo taps of the sub-pixel form in `part`, folded into the 9 kernel taps of dw; up == 2: of a 1 x 1 source
+    // (WgradSel::dead1x1) -- the slices of the dead pseudo taps were never written: +0.f without a load, the same fold
     __shared__ float tile[16][65];
     const int t = threadIdx.x;
     const int ci0 = blockIdx.x * 64, co = blockIdx.y;
@@ -1152,6 +1157,10 @@ __global__ void __launch_bounds__(256) conv3x3_wgrad_tap_reduce_kernel(const flo
     const int c = t & 63;
     const bool c_ok = ci0 + c < C;
     for (int tp = t >> 6; tp < ntaps; tp += 4) {
+        if (up == 2 && !up1x1_live(tp)) {
+            tile[tp][c] = 0.f;
+            continue;
+        }
         const float* src = c_ok ? part + (long)tp * plane + (long)co * C + ci0 + c : part;   // always loadable
         float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
         int sp = 0;
@@ -1180,12 +1189,16 @@ __global__ void __launch_bounds__(256) conv3x3_wgrad_tap_reduce_kernel(const flo
 // summation runs over (elements x groups) threads instead of elements only; the transposing kernel above then sums
 // the groups.  Fixed order inside a group and over the groups (deterministic).
 __global__ void __launch_bounds__(256) conv3x3_wgrad_group_sum_kernel(const float* __restrict__ part, long n, int splits,
-                                                                      int per_group, float* __restrict__ out) {
+                                                                      int per_group, float* __restrict__ out,
+                                                                      long dead_plane) {
+    // dead_plane != 0: [16 pseudo taps][dead_plane] partials of a 1 x 1 source (WgradSel::dead1x1) -- the dead taps' slices hold
+    // nothing: neither read nor summed here (the reduction behind this stage does not read their group sums either)
     const int z = blockIdx.y;
     const int s0 = z * per_group;
     int s1 = s0 + per_group;
     if (s1 > splits) s1 = splits;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        if (dead_plane && !up1x1_live((int)(i / dead_plane))) continue;
         const float* src = part + i;
         float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
         int sp = s0;
@@ -1252,6 +1265,12 @@ __host__ __device__ __forceinline__ void reduce_map(int splits, int* tw, int* ro
 // no LDS, no barrier.  blocks = ceil(Cout * C / 4 / 256).
 __host__ __device__ __forceinline__ bool reduce_flat(int splits, int C) { return splits < 4 && (C & 3) == 0; }
 
+// the pseudo taps of a layout-2 descriptor whose slices hold partials: all 16, or the live four of a 1 x 1 source
+// (MNK_REDUCE_UP1X1: the others were never written; every map takes them as +0.f and performs the same additions)
+__device__ __forceinline__ unsigned reduce_live_taps(const MnkWgradReduceDesc& d) {
+    return (d.layout == 2 && (d.flags & MNK_REDUCE_UP1X1)) ? up1x1_live_mask(false) : 0xffffu;
+}
+
 // out[e * NT + tp] = v[tp].e for the four channels e of a thread: the (tap, ci) -> (ci, tap) transposition in registers
 template <int NT>
 __device__ __forceinline__ void flat_store(const float4* v, float* __restrict__ dst, bool accumulate) {
@@ -1279,7 +1298,7 @@ __device__ __forceinline__ void flat_store(const float4* v, float* __restrict__ 
     }
 }
 
-template <int NIN, int NOUT, int LAYOUT>      // taps read / written; LAYOUT 0 tap-major, 2 tap-major sub-pixel (16 -> 9), 1 parameter-major
+template <int NIN, int NOUT, int LAYOUT, bool UP1X1 = false>      // taps read / written; LAYOUT 0 tap-major, 2 tap-major sub-pixel (16 -> 9), 1 parameter-major
 __device__ __forceinline__ void reduce_flat_body(const MnkWgradReduceDesc& d, int co, int ci) {
     float4 acc[NIN];
 #pragma unroll
@@ -1321,6 +1340,8 @@ __device__ __forceinline__ void reduce_flat_body(const MnkWgradReduceDesc& d, in
     for (int sp = 0; sp < d.splits; ++sp) {                      // NIN independent 16-byte loads in flight per split
 #pragma unroll
         for (int tp = 0; tp < NIN; ++tp) {
+            // UP1X1 (MNK_REDUCE_UP1X1): a dead pseudo tap's slice was never written -- its sum stays the +0.f it would be, no load
+            if (UP1X1 && !up1x1_live(tp)) continue;
             const float4 v = *reinterpret_cast<const float4*>(src + (long)sp * sstride + (long)tp * plane);
             acc[tp] = make_float4(acc[tp].x + v.x, acc[tp].y + v.y, acc[tp].z + v.z, acc[tp].w + v.w);
         }
@@ -1650,7 +1671,9 @@ __global__ void __launch_bounds__(256, 4) wgrad_reduce_multi_kernel(const MnkWgr
         const long item = (long)local * 256 + threadIdx.x;
         if (item >= (long)d.Cout * q4) return;
         const int co = (int)(item / q4), ci = 4 * (int)(item - (long)co * q4);
-        if (d.layout == 2)
+        if (d.layout == 2 && reduce_live_taps(d) != 0xffffu)
+            reduce_flat_body<16, 9, 2, true>(d, co, ci);
+        else if (d.layout == 2)
             reduce_flat_body<16, 9, 2>(d, co, ci);
         else if (d.layout == 0 && d.ntaps == 9)
             reduce_flat_body<9, 9, 0>(d, co, ci);
@@ -1662,8 +1685,11 @@ __global__ void __launch_bounds__(256, 4) wgrad_reduce_multi_kernel(const MnkWgr
             reduce_flat_body<16, 16, 1>(d, co, ci);
         return;
     }
-    // (block-uniform; unaligned partials -- no caller of this library has them -- keep the tile map)
-    const int map = ((size_t)d.part & 15) == 0 ? reduce_map_id(vec, d.layout, d.splits, d.ntaps, d.Cout, d.C) : REDUCE_MAP_TILE;
+    // (block-uniform; unaligned partials -- no caller of this library has them -- keep the tile map; so do the partials of a
+    // 1 x 1 source, MNK_REDUCE_UP1X1: only the flat and the tile map know the slices that hold nothing -- a few frames' worth of
+    // partials per layer, and the same bits on every map)
+    const int map = ((size_t)d.part & 15) == 0 && reduce_live_taps(d) == 0xffffu
+                        ? reduce_map_id(vec, d.layout, d.splits, d.ntaps, d.Cout, d.C) : REDUCE_MAP_TILE;
     if (map == REDUCE_MAP_VEC_TAP) {
         reduce_vec_tap(d, local, sm);
         return;
@@ -1691,6 +1717,25 @@ __global__ void __launch_bounds__(256, 4) wgrad_reduce_multi_kernel(const MnkWgr
 #pragma unroll
         for (int tp = 0; tp < 16; ++tp) acc[tp] = acc2[tp] = 0.f;
         int sp = s0;
+        if (reduce_live_taps(d) != 0xffffu) {
+            // MNK_REDUCE_UP1X1 (block-uniform): the same two chains over the four live pseudo taps; a dead one's sums stay the +0.f
+            // its slice would hold, and nothing of it is loaded
+            for (; sp + sstep < d.splits; sp += 2 * sstep) {
+                const float* ps = src + (long)sp * sstride;
+                const float* pt = ps + (long)sstep * sstride;
+#pragma unroll
+                for (int ph = 0; ph < 4; ++ph) {
+                    acc[up1x1_live_tap(ph)] += ps[(long)up1x1_live_tap(ph) * plane];
+                    acc2[up1x1_live_tap(ph)] += pt[(long)up1x1_live_tap(ph) * plane];
+                }
+            }
+            if (sp < d.splits) {
+                const float* ps = src + (long)sp * sstride;
+#pragma unroll
+                for (int ph = 0; ph < 4; ++ph) acc[up1x1_live_tap(ph)] += ps[(long)up1x1_live_tap(ph) * plane];
+            }
+            sp = d.splits;
+        }
         for (; sp + sstep < d.splits; sp += 2 * sstep) {       // two splits per trip: 2 * ntaps loads in flight
             const float* ps = src + (long)sp * sstride;
             const float* pt = ps + (long)sstep * sstride;
@@ -1902,7 +1947,7 @@ static void launch_wgrad_reduce(float* ws, int splits, int Cout, int NT, float* 
     if (groups) {
         float* part2 = ws + (size_t)splits * n;
         hipLaunchKernelGGL(conv3x3_wgrad_group_sum_kernel, dim3(grid_for(n, 1024), groups), dim3(256), 0, s, ws, n, splits, 8,
-                           part2);
+                           part2, 0L);
         src = part2;
         nsum = groups;
     }
@@ -1948,6 +1993,12 @@ static bool tap_compact_ok(int H, int W, long M, int kh, int kw, int pad, int up
     if (g_wtap_compact <= 0 || (long)H * W > g_wtap_compact || M >= (1L << 20)) return false;
     return subpix || (!ups && kh == 3 && kw == 3 && pad == 1);
 }
+// 1: a sub-pixel job on a 1 x 1 low-resolution source makes tiles for its four live pseudo taps only (pack_tile.h: up1x1_live) and
+// the readers of its partials, and the optimiser kernel's pack emission, leave the dead slices alone; 0: all 16, as for any source
+static int g_up1x1_dead_taps = tuning_knob("up1x1_dead_taps", &g_up1x1_dead_taps, 1);
+// ONE rule for the GEMM that leaves the dead slices unwritten and for everybody who must then not read them (H, W: the low
+// resolution; the tile index of the live taps lives in the compact K form)
+static bool up1x1_skips(int H, int W, long M) { return g_up1x1_dead_taps && H == 1 && W == 1 && tap_compact_ok(H, W, M, 3, 3, 1, 0, 1); }
 // (pixel, tap) pairs a compact job multiplies: 3x3 pad 1: (3H - 2)(3W - 2) per frame; sub-pixel form (offsets {-1, 0} / {0, +1}
 // per phase and axis): (4H - 2)(4W - 2) per frame
 static double tap_compact_pairs(long frames, int H, int W, int subpix) {
@@ -1987,6 +2038,8 @@ struct WgradSel {
     long M, pix_per_split;
     int splits;             // split partials the GEMM leaves behind; 0: it writes dw itself (nothing to reduce)
     int layout;             // of the partials (MnkWgradPlan::layout)
+    bool dead1x1;           // WG_SUBPIX on a 1 x 1 source (up1x1_skips): tiles of the four live pseudo taps only, the dead slices of
+                            // the partials stay unwritten -- the reduction must carry MNK_REDUCE_UP1X1
     size_t part_floats;     // the partials = the workspace of the single-layer entry under MNK_WGRAD_DEFER
     size_t ws_floats;       // ... and without it: + the group sums of a two-stage reduction
 };
@@ -2055,6 +2108,7 @@ static WgradSel wgrad_select(const MnkWgradJob& j, bool aligned, bool grouped) {
             s.splits = s.t.splits, s.pix_per_split = s.t.pix_per_split;
             if (grouped) grouped_split(s.M, &s.splits, &s.pix_per_split);
             s.mode = tap_mode(s, j, subpix);
+            s.dead1x1 = subpix && up1x1_skips(s.H, s.W, s.M);
             if (grouped) s.variant = 4 * tap_tile_id(s.t) + s.mode;
         } else if (k3 && (!grouped || g_wn16_group_target > 0)) {
             s.n = make_nplan(j.N, j.Ho, j.Wo, j.Cout, j.C, j.ld_x, grouped ? n16_group_target(j.Cout, j.C) : 0);
@@ -2081,6 +2135,9 @@ static WgradSel wgrad_select(const MnkWgradJob& j, bool aligned, bool grouped) {
     return s;
 }
 
+// tiles of a tap-major job along its taps
+static int tap_tiles(const WgradSel& s) { return s.dead1x1 ? 4 : s.ntaps; }
+
 static void fill_tap_args(WgradTapArgs& g, const MnkWgradJob& j, const WgradSel& s, int xcd) {
     const bool subpix = s.form == WG_SUBPIX;
     const int ups = subpix ? 0 : (j.flags & MNK_CONV_UPSAMPLED);        // the sub-pixel form reads the source as it is
@@ -2092,7 +2149,7 @@ static void fill_tap_args(WgradTapArgs& g, const MnkWgradJob& j, const WgradSel&
     fast_div_consts((unsigned)s.W, &g.mulW, &g.shW);
     fast_div_consts((unsigned)s.H, &g.mulH, &g.shH);
     g.sw = s.sw, g.sh = s.sh, g.sn = s.sn;
-    g.compact = tap_compact_ok(s.H, s.W, s.M, j.kh, j.kw, j.pad, ups, subpix) ? 1 : 0;
+    g.compact = tap_compact_ok(s.H, s.W, s.M, j.kh, j.kw, j.pad, ups, subpix) ? (s.dead1x1 ? 2 : 1) : 0;
     g.nsplits = s.splits;
 }
 
@@ -2133,7 +2190,8 @@ static void launch_tap_tile_grouped(int mode, int blocks, hipStream_t st, const 
 }
 
 // sum the `splits` tap-major partials at ws into dw (fold: the 16 pseudo taps of the sub-pixel form into the nine kernel taps):
-// optional first stage over groups of 8 splits, then the (tap, ci) -> (ci, tap) transposing reduction
+// optional first stage over groups of 8 splits, then the (tap, ci) -> (ci, tap) transposing reduction.  fold == 2: the partials of
+// a 1 x 1 source (WgradSel::dead1x1) -- neither stage reads the slices of the dead pseudo taps
 static void launch_tap_reduce(float* ws, int splits, int ntaps, int Cout, int C, float* dst, long ld_out, int fold, hipStream_t s) {
     const long n = (long)ntaps * Cout * C;
     const float* src = ws;
@@ -2142,7 +2200,7 @@ static void launch_tap_reduce(float* ws, int splits, int ntaps, int Cout, int C,
     if (groups) {
         float* part2 = ws + (size_t)splits * n;
         hipLaunchKernelGGL(conv3x3_wgrad_group_sum_kernel, dim3(grid_for(n, 1024), groups), dim3(256), 0, s, ws, n, splits, 8,
-                           part2);
+                           part2, fold == 2 ? (long)Cout * C : 0L);
         src = part2;
         nsum = groups;
     }
@@ -2227,7 +2285,7 @@ int mnk_conv2d_wgrad(const float* x, int ld_x, int C, int flags, int Hi, int Wi,
             const bool subpix = s.form == WG_SUBPIX;      // (its 16 pseudo taps run at the low resolution)
             ProfScope prof(K_CONV_WGRAD, st, flop, g.compact ? 2.0 * tap_compact_pairs(N, s.H, s.W, subpix) * Cout * C
                                                    : subpix ? 2.0 * (double)s.M * Cout * 16.0 * C : -1.0);
-            const dim3 grid(s.t.gm, s.t.gn * s.ntaps, s.splits);
+            const dim3 grid(s.t.gm, s.t.gn * tap_tiles(s), s.splits);
             switch (tap_tile_id(s.t)) {
                 case 0: launch_tap_tile<128, 128, 2, 2>(s.mode, grid, st, g, one_plane); break;
                 case 1: launch_tap_tile<128, 64, 2, 2>(s.mode, grid, st, g, one_plane); break;
@@ -2281,7 +2339,7 @@ int mnk_conv2d_wgrad(const float* x, int ld_x, int C, int flags, int Hi, int Wi,
         const bool tap_major = s.form <= WG_N16;        // (the tap-major forms' figure counts the write of dw too)
         ProfScope prof(K_CONV_REDUCE, st, (double)(s.splits + (s.form <= WG_TAP ? 1 : 0)) * s.ntaps * Cout * C * 4);
         if (tap_major)
-            launch_tap_reduce(ws, s.splits, s.ntaps, Cout, C, dst, ld_dst, s.form == WG_SUBPIX, st);
+            launch_tap_reduce(ws, s.splits, s.ntaps, Cout, C, dst, ld_dst, s.form == WG_SUBPIX ? (s.dead1x1 ? 2 : 1) : 0, st);
         else
             launch_wgrad_reduce(ws, s.splits, Cout, NT, dst, ld_dst, st);
     }
@@ -2362,7 +2420,7 @@ int mnk_wgrad_grouped_build(const MnkWgradJob* jobs, int n, void* host_table, si
             TapJobRec& r = recs[k];
             fill_tap_args(r.a, j, s, 0);
             r.gm = s.t.gm;
-            r.gnt = s.t.gn * s.ntaps;
+            r.gnt = s.t.gn * tap_tiles(s);
             r.splits = s.splits;
             r.block_begin = blocks;
             blocks += r.gm * r.gnt * r.splits;
@@ -2442,6 +2500,12 @@ int mnk_wgrad_reduce_blocks(int splits, int Cout, int C) {
 int mnk_wgrad_reduce_map(int layout, int splits, int ntaps, int Cout, int C) {
     if (splits <= 0 || Cout <= 0 || C <= 0 || ntaps <= 0) return -1;
     return reduce_map_id(g_wgrad_reduce_vec != 0, layout, splits, ntaps, Cout, C);
+}
+
+int mnk_up1x1_live_mask(int dgrad) { return (int)up1x1_live_mask(dgrad != 0); }
+
+int mnk_up1x1_dead_taps(int N, int Hs, int Ws) {
+    return N > 0 && Hs > 0 && Ws > 0 && up1x1_skips(Hs, Ws, (long)N * Hs * Ws) ? 1 : 0;
 }
 
 int mnk_wgrad_reduce_multi(const MnkWgradReduceDesc* descs_device, int n, int total_blocks, void* stream) {

@@ -147,11 +147,14 @@ __global__ void __launch_bounds__(256) adam_multi_kernel(const MnkAdamDesc* __re
         const int nin = (d.flags & (g.second ? 4 : 2)) ? 16 : 9;
         const int splits = g.second ? d.gt_splits1 : d.gt_splits0;
         const long plane = (long)d.Cout * g.Cs, sstride = (long)nin * plane;
+        // MNK_ADAM_UP1X1: the GEMM made no tiles for the dead pseudo taps of a 1 x 1 source -- their slices hold nothing and
+        // count as the +0.f they would hold (the same additions below, none of the loads)
+        const unsigned live = (nin == 16 && (d.flags & MNK_ADAM_UP1X1)) ? up1x1_live_mask(false) : 0xffffu;
         for (int i = t; i < nin * 256; i += 256) {
             const int ci = i & 15, r = (i >> 4) & 15, tp = i >> 8;
             const int co = g.co0 + r, c = g.ci0 + ci;
             float v = 0.f;
-            if (co < d.Cout && c < g.Cs) {
+            if (co < d.Cout && c < g.Cs && ((live >> tp) & 1)) {
                 const float* src = gt + ((long)tp * d.Cout + co) * g.Cs + c;
                 for (int sp = 0; sp < splits; ++sp) v += src[(long)sp * sstride];
             }
@@ -188,7 +191,7 @@ __global__ void __launch_bounds__(256) adam_multi_kernel(const MnkAdamDesc* __re
     }
     __syncthreads();
     if (d.flags & 1)       // an up-sampled convolution (UpBlock3D): the packs of its sub-pixel forms
-        pack_tile_emit_up(T, g, d.wp_fwd, d.wp_d0, d.wp_d1, d.Cout, cc, cot);
+        pack_tile_emit_up(T, g, d.wp_fwd, d.wp_d0, d.wp_d1, d.Cout, cc, cot, (d.flags & MNK_ADAM_UP1X1) != 0);
     else
         pack_tile_emit<9>(T, g, d.wp_fwd, d.wp_d0, d.wp_d1, d.Cout, cc, cot);
 }

@@ -74,6 +74,36 @@ __device__ __forceinline__ void up_dgrad_set(int t, int& lo, int& hi) {
     hi = t == 0 ? 2 : (t == 1 ? 2 : (t == 2 ? 1 : 0));
 }
 
+// ---- a 1 x 1 low-resolution source: the pseudo taps that only ever meet padding ("up1x1_dead_taps", conv3x3_wgrad.hip) --------
+// Every loader of the sub-pixel forms has one padding rule per axis: a tap that reads entry e of an axis of `len` entries is
+// inside iff 0 <= e < len (conv3x3.hip: count_row_taps; conv3x3_wgrad.hip: MODE 3).  On a 1 x 1 source the position is 0, so
+//   forward / weight gradient: pseudo tap (a, u) reads low-resolution entry 0 + a - 1 + u of 1,
+//   data gradient: tap t (4x4, stride 2, pad 1 over the 2 x 2 dy) reads dy entry 2 * 0 + t - 1 of 2.
+// A tap that is outside on either axis is DEAD: its weight-gradient partial is an exact +0.f and no GEMM needs its pack slice.
+// This is the one definition; the weight-gradient tiles, the readers of their partials and pack_tile_emit_up use it.
+__host__ __device__ constexpr bool up1x1_axis_live(int a, int u) { return a - 1 + u >= 0 && a - 1 + u < 1; }
+__host__ __device__ constexpr bool up1x1_axis_live_dgrad(int t) { return t - 1 >= 0 && t - 1 < 2; }
+// pseudo tap 4 * (2a + b) + 2u + v of the forward / weight-gradient form
+__host__ __device__ constexpr bool up1x1_live(int tap) {
+    return up1x1_axis_live((tap >> 3) & 1, (tap >> 1) & 1) && up1x1_axis_live((tap >> 2) & 1, tap & 1);
+}
+// tap16 = 4 ty + tx of the data-gradient form
+__host__ __device__ constexpr bool up1x1_live_dgrad(int tap16) {
+    return up1x1_axis_live_dgrad(tap16 >> 2) && up1x1_axis_live_dgrad(tap16 & 3);
+}
+// the live pseudo tap of a phase (there is exactly one: static_assert below)
+__host__ __device__ constexpr int up1x1_live_tap(int phase) {
+    return up1x1_live(4 * phase) ? 4 * phase : (up1x1_live(4 * phase + 1) ? 4 * phase + 1 : (up1x1_live(4 * phase + 2) ? 4 * phase + 2 : 4 * phase + 3));
+}
+__host__ __device__ constexpr unsigned up1x1_live_mask(bool dgrad, int tap = 0) {
+    return tap == 16 ? 0u : (((dgrad ? up1x1_live_dgrad(tap) : up1x1_live(tap)) ? 1u << tap : 0u) | up1x1_live_mask(dgrad, tap + 1));
+}
+constexpr bool up1x1_one_live_tap_per_phase(int phase = 0) {
+    return phase == 4 || ((up1x1_live(4 * phase) + up1x1_live(4 * phase + 1) + up1x1_live(4 * phase + 2) + up1x1_live(4 * phase + 3)) == 1 &&
+                          up1x1_one_live_tap_per_phase(phase + 1));
+}
+static_assert(up1x1_one_live_tap_per_phase(), "a 1 x 1 source leaves one live pseudo tap per phase");
+
 // ---- the weight gradient of the sub-pixel form (16 pseudo taps) folded into the nine kernel taps ------------------------------
 // the pseudo taps of the sub-pixel form that contribute to kernel row (column) k: (a, u) with k in S(a, u) -- two each
 __device__ __forceinline__ void up_fold_pairs(int k, int& a0, int& u0, int& a1, int& u1) {
@@ -94,13 +124,16 @@ __device__ __forceinline__ float up_fold(const float* acc, int ky, int kx, int s
     return v;
 }
 
+// dead1x1: the layer runs on a 1 x 1 source -- the slices of its dead taps are not stored (they keep what a full pack left there:
+// finite, stale values that the tap-skipping GEMMs never read and every other form multiplies by the zeros of the padding)
 __device__ __forceinline__ void pack_tile_emit_up(const float* T, const PackTileGeom& g, float* __restrict__ wf,
-                                                  float* __restrict__ wd0, float* __restrict__ wd1, int Cout, int cc, int cot) {
+                                                  float* __restrict__ wd0, float* __restrict__ wd1, int Cout, int cc, int cot,
+                                                  bool dead1x1 = false) {
     const int t = threadIdx.x;
     for (int i = t; i < 4096; i += 256) {           // forward: 16 co x 4 phases x 4 taps x 16 ci
         const int k16 = i & 15, tap4 = (i >> 4) & 3, phase = (i >> 6) & 3, r = i >> 8;
         const int co = g.co0 + r;
-        if (co >= Cout) continue;
+        if (co >= Cout || (dead1x1 && !up1x1_live(4 * phase + tap4))) continue;
         int y0, y1, x0, x1;
         up_phase_set(phase >> 1, tap4 >> 1, y0, y1);
         up_phase_set(phase & 1, tap4 & 1, x0, x1);
@@ -115,7 +148,7 @@ __device__ __forceinline__ void pack_tile_emit_up(const float* T, const PackTile
         for (int i = t; i < 4096; i += 256) {       // data gradient: 16 ci x 16 taps x 16 co
             const int k16 = i & 15, tap16 = (i >> 4) & 15, r = i >> 8;
             const int ci = g.ci0 + r;
-            if (ci >= g.Cs) continue;
+            if (ci >= g.Cs || (dead1x1 && !up1x1_live_dgrad(tap16))) continue;
             int y0, y1, x0, x1;
             up_dgrad_set(tap16 >> 2, y0, y1);
             up_dgrad_set(tap16 & 3, x0, x1);

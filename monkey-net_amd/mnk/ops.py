@@ -291,6 +291,7 @@ def _after_optimizer_step(opt, args, kwargs):
     if fresh:
         for e in fresh:
             w = e.wref()
+            e.partial = adam_desc_flags(e) & 8 != 0      # what the kernel's table said (it is keyed by the registry version)
             if w is not None and e.wptr == w.data_ptr():
                 e.stamp = w._version
         opt._mnk_fresh_entries = ()
@@ -340,6 +341,13 @@ def pack_entry_of(p):
     if e is not None and e.wref() is p and e.wptr == p.data_ptr():
         return e
     return None
+
+
+def adam_desc_flags(e):
+    """MnkAdamDesc::flags of a packed-weight entry, without the gt bits: bit 0 = the packs of the sub-pixel forms, bit 3
+    (MNK_ADAM_UP1X1) = leave the dead slices of a 1 x 1 source alone.  One place for mnk.optim.MnkAdam and AdoptedAdam."""
+    up = bool(e.meta[3])
+    return int(up) | (8 if up and e.dead1x1 else 0)
 
 
 def subpixel(ups):
@@ -417,9 +425,32 @@ def _packed_fwd_weight(weight, cout, c0, c1, up=False):
     return wp
 
 
+def up1x1_dead_taps(n, hs, ws):
+    """An up-sampled convolution of n frames on an hs x ws LOW-resolution source leaves the dead pseudo taps of a 1 x 1 source out
+    (the library's rule, mnk_up1x1_dead_taps: its weight-gradient GEMM writes no partials for them, so their readers must not
+    load them).  Read once per library handle and mnk_set_tuning call, like subpixel()."""
+    if hs != 1 or ws != 1:
+        return False
+    lib = _lib.lib()
+    epoch = getattr(lib, "tuning_epoch", 0)
+    hit = getattr(lib, "_up1x1_cache", None)
+    if hit is None or hit[0] != epoch:
+        hit = lib._up1x1_cache = (epoch, {})
+    if n not in hit[1]:
+        hit[1][n] = bool(lib.query("mnk_up1x1_dead_taps", n, 1, 1))
+    return hit[1][n]
+
+
 class _PackEntry:
-    """Persistent packed copies (forward + data-gradient layouts) of one conv parameter used by training forwards."""
-    __slots__ = ("wref", "wptr", "meta", "ntaps", "wp", "wd", "stamp", "__weakref__")
+    """Persistent packed copies (forward + data-gradient layouts) of one conv parameter used by training forwards.
+    The three fields of an up-sampled convolution that runs on a 1 x 1 source (up1x1_dead_taps):
+      dead1x1  the geometry the weight was LAST used at lets the optimiser kernel leave the dead slices of the packs alone
+               (MnkAdamDesc bit 3); a change bumps pack_registry_version(), which the optimisers' tables are keyed by;
+      partial  the last emission did: the dead slices hold finite values of an earlier, full pack -- only meaningful while the
+               entry is fresh (a stale entry is packed in full before any use);
+      full     a forward has needed the dead slices of a partial entry (the same weight on a larger source): it was packed in
+               full, and dead1x1 stays off for this weight from then on."""
+    __slots__ = ("wref", "wptr", "meta", "ntaps", "wp", "wd", "stamp", "dead1x1", "partial", "full", "__weakref__")
 
     def same(self, weight, meta, ntaps):
         return self.wref() is weight and self.wptr == weight.data_ptr() and self.meta == meta and self.ntaps == ntaps
@@ -435,17 +466,35 @@ class _PackEntry:
 
 
 
-def _pack_entry(weight, cout, c0, c1, need, up=False, ntaps=9):
+def _note_geometry(e, dead):
+    """A forward uses entry `e`; dead: on a geometry whose dead slices nobody reads (up1x1_dead_taps).  Records the geometry for
+    the next optimiser step and answers whether the packs can be used as they are -- False: this use needs slices that the last
+    emission left out."""
+    want = bool(dead) and not e.full
+    usable = want or not e.partial
+    if not usable:
+        e.full, want = True, False
+    if e.dead1x1 != want:
+        e.dead1x1 = want
+        _PACK_REG_VERSION[0] += 1          # the optimisers' descriptor tables carry the bit
+    return usable
+
+
+def _pack_entry(weight, cout, c0, c1, need, up=False, ntaps=9, dead1x1=False):
     """The (packed, up to date) registry entry of `weight`: packs with one per-layer launch unless the entry is fresh
     (repack_registered() ran since the last optimiser step).  up: the packs of the sub-pixel forms of an up-sampled
-    convolution (mnk_conv3x3_up_fwd / _up_dgrad) instead of the 3x3 layouts.  ntaps != 9: a K x K weight (ConvKxKFn)."""
+    convolution (mnk_conv3x3_up_fwd / _up_dgrad) instead of the 3x3 layouts.  ntaps != 9: a K x K weight (ConvKxKFn).
+    dead1x1: this forward and its backward run on a 1 x 1 source (up1x1_dead_taps; see _PackEntry)."""
     meta = (cout, c0, c1, bool(up))
     kxk = ntaps != 9
     form, dform = (_FORMS["up"], _FORMS["up_dgrad"]) if up else (_FORMS["3x3"], _FORMS["3x3"])
     e = _PACK_REG.get(id(weight))
-    if e is not None and e.fresh(weight, meta, need, ntaps):
+    known = e is not None and e.same(weight, meta, ntaps)
+    # (a fresh entry whose last emission was partial and whose dead slices are needed now takes the stale entry's way: one launch)
+    usable = _note_geometry(e, dead1x1) if known else True
+    if usable and e is not None and e.fresh(weight, meta, need, ntaps):
         return e
-    if (e is not None and e.same(weight, meta, ntaps)
+    if (known
             and all(e.wd[i] is not None for i in (0, 1) if need[i])):
         # a known layer gone stale (an optimiser stepped): the first such layer of an iteration re-packs EVERY registered
         # parameter in one launch -- a user-owned loop (the reference's train.py) then pays one pack launch per iteration
@@ -456,6 +505,7 @@ def _pack_entry(weight, cout, c0, c1, need, up=False, ntaps=9):
         e = _PackEntry()
         e.wref, e.wptr, e.meta, e.wd, e.stamp = weakref.ref(weight), weight.data_ptr(), meta, [None, None], None
         e.ntaps = ntaps
+        e.dead1x1, e.partial, e.full = bool(dead1x1), False, False
         nf = _query(_FORMS["kxk"].packed, cout, c0, c1, ntaps) if kxk else _query(form.packed, cout, c0, c1)
         e.wp = torch.empty(nf, dtype=torch.float32, device=weight.device)
         key = id(weight)
@@ -482,6 +532,7 @@ def _pack_entry(weight, cout, c0, c1, need, up=False, ntaps=9):
     else:
         _call("mnk_conv3x3_pack_all", weight, _p(weight), _p(e.wp), _p(e.wd[0]), _p(e.wd[1]), cout, c0, c1)
     e.stamp = None            # only repack_registered() vouches for freshness: a user-owned loop packs on every call
+    e.partial = False         # (every pack launch of this module writes all slices; only the optimiser kernel leaves some out)
     return e
 
 
@@ -538,6 +589,7 @@ def repack_registered(only_if_stale=False):
             e.pack()
     for e in t["entries"] + t["kxk"]:
         w = e.wref()
+        e.partial = False
         if w is not None:
             e.stamp = w._version
     return True
@@ -877,7 +929,7 @@ class Conv3x3Fn(_Fn):
             # a backward will follow: the parameter changes every step -> packed per iteration (forward + the
             # data-gradient layouts the backward will need), by repack_registered() or one launch here
             need = [bool(cc and ctx.needs_input_grad[i]) for i, cc in enumerate((c0, c1))]
-            e = _pack_entry(weight, cout, c0, c1, need, up)
+            e = _pack_entry(weight, cout, c0, c1, need, up, dead1x1=up and up1x1_dead_taps(n, hs, ws_))
             wp, ctx.wd = e.wp, list(e.wd)
         else:
             wp = _packed_fwd_weight(weight, cout, c0, c1, up)

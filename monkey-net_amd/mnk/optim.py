@@ -31,7 +31,7 @@ ADAM_DESC = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("
                       ("gt_splits0", "<i4"), ("gt_splits1", "<i4")])
 REDUCE_DESC = np.dtype([("part", "<u8"), ("dw", "<u8"), ("layout", "<i4"), ("splits", "<i4"), ("ntaps", "<i4"),
                         ("Cout", "<i4"), ("C", "<i4"), ("Cin_total", "<i4"), ("c_start", "<i4"), ("accumulate", "<i4"),
-                        ("block_begin", "<i4"), ("reserved", "<i4")])
+                        ("block_begin", "<i4"), ("flags", "<i4")])
 
 
 JOB = np.dtype([("x", "<u8"), ("dy", "<u8"), ("part", "<u8"), ("part_floats", "<u8"), ("ld_x", "<i4"), ("C", "<i4"),
@@ -119,8 +119,11 @@ class DeferredReducer:
                 raise _lib.MnkError("mnk_conv2d_wgrad_plan2 failed: %s" % lib.cdll.mnk_last_error().decode())
             layout, splits, nfloats = int(plan.layout), int(plan.splits), int(plan.part_floats)
         part = torch.empty(max(nfloats, 1), dtype=torch.float32, device=weight.device)
+        # MNK_REDUCE_UP1X1: the sub-pixel GEMM of a 1 x 1 source leaves the dead pseudo taps' slices of `part` unwritten
+        up1x1 = int(layout == 2 and mops.up1x1_dead_taps(n, ho // 2, wo // 2))
         rec = {"shape": shape, "part": part, "splits": splits, "nfloats": nfloats, "grouped": grouped, "job": job,
                "direct_ok": mops.pack_entry_of(weight) is not None and c_start in (0, mops.pack_entry_of(weight).meta[1]),
+               "up1x1": up1x1, "tuning": getattr(lib, "tuning_epoch", 0), "wref": weakref.ref(weight),
                "row": (part.data_ptr(), sink.data_ptr(), layout, splits, kh * kw, cout, c, cin_total, c_start, 0),
                "blocks": lib.query("mnk_wgrad_reduce_blocks", splits, cout, c) if splits > 0 else 0}
         self.recs[key] = rec
@@ -143,7 +146,8 @@ class DeferredReducer:
             return False
         shape = (n, ho, wo, c, cout, kh, kw, pad, ld_x, cin_total, hi, wi, ld_dy, c_start)
         rec = self.recs.get(key)
-        if rec is None or rec["shape"] != shape:
+        # (a record holds what the library's plan said, and the plan follows the tuning values: mnk_set_tuning makes it anew)
+        if rec is None or rec["shape"] != shape or rec["tuning"] != getattr(_lib.lib(), "tuning_epoch", 0):
             rec = self._record(key, weight, sink, shape, int(flags))
         if rec["grouped"]:
             # the plan does not depend on MNK_WGRAD_BF16 (bit 3): the job carries the bit of THIS backward pass
@@ -169,8 +173,14 @@ class DeferredReducer:
         r = self.recs.get(key)
         # C % 4 == 0: only the layers mnk_wgrad_reduce_multi sums with its flat map -- (s0 + s1) + s2 in split order, the order
         # the optimiser kernel's direct read uses; the tile map of the other layers adds (s0 + s2) + s1, an ulp apart
-        return (r is not None and r["grouped"] and 1 <= r["splits"] <= 3 and r["row"][2] in (0, 2) and r["row"][4] == 9
-                and r["row"][6] % 4 == 0 and r["direct_ok"] and key not in self.multi)
+        if not (r is not None and r["grouped"] and 1 <= r["splits"] <= 3 and r["row"][2] in (0, 2) and r["row"][4] == 9
+                and r["row"][6] % 4 == 0 and r["direct_ok"] and key not in self.multi):
+            return False
+        # MnkAdamDesc has ONE 1 x 1-source bit for the partials it reads and the packs it emits: partials with unwritten dead slices
+        # go with an entry that was last used on a 1 x 1 source, and complete ones with any other
+        w = r["wref"]()
+        e = mops.pack_entry_of(w) if w is not None else None
+        return r["row"][2] != 2 or (e is not None and bool(r["up1x1"]) == bool(mops.adam_desc_flags(e) & 8))
 
     def _launch_grouped(self, background=False):
         jobs, self.jobs = self.jobs, []
@@ -244,7 +254,7 @@ class DeferredReducer:
             blocks = 0
             for i, k in enumerate(keys):
                 r = self.recs[k]
-                rec[i] = r["row"] + (blocks, 0)
+                rec[i] = r["row"] + (blocks, r["up1x1"])
                 blocks += r["blocks"]
             tab = (_device_table(rec, dev, self.keep), len(keys), blocks)
             self.tables[keys] = tab
@@ -265,7 +275,7 @@ class DeferredReducer:
         blocks = 0
         for i, k in enumerate(keys):
             r = self.recs[k]
-            rec[i] = r["row"] + (blocks, 0)
+            rec[i] = r["row"] + (blocks, r["up1x1"])
             blocks += r["blocks"]
         dev = self.recs[keys[0]]["part"].device
         tab = _device_table(rec, dev, self.keep)
@@ -434,13 +444,15 @@ class MnkAdam(torch.optim.Optimizer, FlatGrads):
             if e is not None:
                 cout, c0, c1, up = e.meta
                 nb = _lib.lib().query("mnk_adam_blocks", 0, cout, c0, c1, 1)
-                gt, flags = [(0, 0), (0, 0)], int(up)
+                gt, flags = [(0, 0), (0, 0)], mops.adam_desc_flags(e)
                 for si, cs in enumerate((0, c0) if c1 else (0,)):
                     key = (id(p), cs)
                     if key in self.reducer.direct:
                         r = self.reducer.recs[key]
                         gt[si] = (r["part"].data_ptr(), r["splits"])
                         flags |= (2 << si) if r["row"][2] == 2 else 0
+                        # (DeferredReducer.is_direct: the kernel skips the dead slices of exactly the partials that lack them)
+                        assert r["row"][2] != 2 or bool(r["up1x1"]) == bool(flags & 8)
                 rows.append((p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), e.wp.data_ptr(),
                              e.wd[0].data_ptr() if e.wd[0] is not None else 0,
                              e.wd[1].data_ptr() if e.wd[1] is not None else 0, cout, c0, c1, blocks, flags, _desc_taps(e),
@@ -503,8 +515,9 @@ class MnkAdam(torch.optim.Optimizer, FlatGrads):
             mdist.all_reduce_flat_(self.flat_grad)          # sum over ranks; the mean is folded into the update
         if not _capturing(self.device):
             self.sync_scalars(1.0 / ws)
+        # (the partials the kernel reads itself are part of the table: a layer recorded anew -- another input size -- has new ones)
         key = (tuple(id(p) for p in active), tuple(p.data_ptr() for p in active), mops.pack_registry_version(),
-               self.reducer.direct)
+               tuple((k, self.reducer.recs[k]["part"].data_ptr(), self.reducer.recs[k]["splits"]) for k in self.reducer.direct))
         if self._table is None or self._table[0] != key:
             if _capturing(self.device):
                 raise RuntimeError("the optimiser's tensor set changed during hipGraph capture (run one eager iteration first)")
@@ -655,8 +668,8 @@ class AdoptedAdam:
                     nb = _lib.lib().query("mnk_adam_blocks", 0, cout, c0, c1, 1)
                     rows.append((p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(),
                                  e.wp.data_ptr(), e.wd[0].data_ptr() if e.wd[0] is not None else 0,
-                                 e.wd[1].data_ptr() if e.wd[1] is not None else 0, cout, c0, c1, blocks, int(up), _desc_taps(e),
-                                 0, 0, 0, 0))
+                                 e.wd[1].data_ptr() if e.wd[1] is not None else 0, cout, c0, c1, blocks, mops.adam_desc_flags(e),
+                                 _desc_taps(e), 0, 0, 0, 0))
                     entries.append(e)
                 else:
                     nb = _lib.lib().query("mnk_adam_blocks", p.numel(), 0, 0, 0, 0)

@@ -45,7 +45,7 @@ def main():
         rec = np.zeros(len(sel), dtype=optim.REDUCE_DESC)
         blocks = 0
         for i, (k, r) in enumerate(sel):
-            rec[i] = r["row"] + (blocks, 0)
+            rec[i] = r["row"] + (blocks, r["up1x1"])
             blocks += r["blocks"]
         t = torch.from_numpy(rec.view(np.uint8).reshape(-1).copy()).cuda()
         return t, len(sel), blocks
