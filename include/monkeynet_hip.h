@@ -265,6 +265,32 @@ int mnk_conv3x3_up_splits(int N, int H, int W, int C0, int C1, int Cout);
 int mnk_conv3x3_fwd(const float* x0, int ld0, int C0, const float* x1, int ld1, int C1, int flags, const float* wp,
                     const float* bias, const float* residual, int ld_res, float* y, int ld_y, int N, int H, int W,
                     int Cout, float* ws, size_t ws_floats, float* stats_partial, void* stream);
+/* ---- forward launches that apply the EVALUATION-mode norm layer behind them (opt-in inference fusion) ---------------------------
+ * In evaluation mode the norm layer behind a convolution (sync_batchnorm/batchnorm.py:50-53 with running statistics) is a constant
+ * per-channel affine; DownBlock3D, UpBlock3D and ResBlock3D (modules/util.py:103-108, 83-88, 63-65) follow it with a ReLU and, in
+ * a DownBlock3D, a (1,2,2) average pool.  These entries are mnk_conv3x3_fwd / mnk_conv3x3_up_fwd without residual and statistics
+ * whose epilogue stores
+ *     z = act(fmaf(v - mean[co], scale[co], beta[co]))          v = what the plain launch stores, act = ReLU when `relu`
+ * (with `pool`: the mean of the four z of a 2x2 window, added in row order, times 1/4) and never writes the convolution's own
+ * output: one crossing of memory instead of three.  mean / scale / beta: mnk_bn_eval_coeffs and the layer's bias.  z is
+ * (N, H, W, ld_z) -- (N, H/2, W/2, ld_z) with `pool`, (N, 2H, 2W, ld_z) for the sub-pixel entry, whose (H, W) is the LOW
+ * resolution -- with ld_z as ld_y of the plain entries; pad channels [Cout, ld_z) are written as zeros.  The result equals
+ * mnk_conv3x3_fwd (mnk_conv3x3_up_fwd) followed by mnk_bn_act_fwd bit for bit (up to the sign of a zero), with the same `flags`:
+ * MNK_CONV_UPSAMPLED | MNK_CONV_CLEAN_PADS | MNK_CONV_BF16 (sub-pixel entry: 0 or MNK_CONV_BF16).
+ * Only an unsplit launch through the buffer-load loaders (MNK_CONV_CLEAN_PADS) can do this, and a pooled one needs a kernel whose
+ * rows walk the pool windows (the plain 3x3 loader, no position-major plan, H and W even).  mnk_conv3x3_evalnorm_form says what a launch at this shape does under the
+ * current tuning -- 0: it is refused (MNK_EINVAL, nothing launched, nothing computed another way: run the two plain entries);
+ * 1: per element; 2: with the pool -- for sources as this library writes them (16-byte aligned, ld = round_up(C, 4)); `up` != 0
+ * asks about the sub-pixel entry, (H, W) its low resolution.  mnk_conv3x3_last_evalnorm_form: the form of the last forward or
+ * data-gradient launch (0: a plain one). */
+int mnk_conv3x3_evalnorm_form(int N, int H, int W, int C0, int C1, int Cout, int flags, int up, int pool);
+int mnk_conv3x3_last_evalnorm_form(void);
+int mnk_conv3x3_fwd_evalnorm(const float* x0, int ld0, int C0, const float* x1, int ld1, int C1, int flags, const float* wp,
+                             const float* bias, const float* mean, const float* scale, const float* beta, int relu, int pool,
+                             float* z, int ld_z, int N, int H, int W, int Cout, void* stream);
+int mnk_conv3x3_up_fwd_evalnorm(const float* x0, int ld0, int C0, const float* x1, int ld1, int C1, int flags, const float* wp_up,
+                                const float* bias, const float* mean, const float* scale, const float* beta, int relu, float* z,
+                                int ld_z, int N, int H, int W, int Cout, void* stream);
 /* dw[co][c_start+ci][ky][kx] = sum_pixels dy[p][co] * x[p+tap][ci]; x is one source (C channels)
  * `flags`: MNK_CONV_UPSAMPLED | MNK_CONV_CLEAN_PADS | MNK_WGRAD_DEFER | MNK_WGRAD_BF16 (below) */
 size_t mnk_conv3x3_wgrad_workspace_floats(int N, int H, int W, int C, int Cout);

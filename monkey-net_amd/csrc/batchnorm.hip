@@ -424,14 +424,9 @@ __global__ void __launch_bounds__(256) bn_eval_coeffs_kernel(const float* __rest
     scale[c] = gamma[c] * is;
 }
 
-__device__ __forceinline__ float act_apply(float v, float slope) {   // slope < 0: identity; 0: ReLU; > 0: LeakyReLU
-    return (slope >= 0.f && !(v > 0.f)) ? v * slope : v;
-}
-
-// z = act((y - mean) * scale + beta) -- THE apply formula of every forward form; bn_apply4: of one channel quad
-__device__ __forceinline__ float bn_apply1(float v, float m, float sc, float be, float slope) {
-    return act_apply(fmaf(v - m, sc, be), slope);
-}
+// (act_apply and bn_apply1 -- z = act((y - mean) * scale + beta), THE apply formula of every forward form -- live in mnk_common.h:
+// the convolution epilogue of an evaluation-mode launch applies the same expression)
+// bn_apply4: bn_apply1 of one channel quad
 __device__ __forceinline__ float4 bn_apply4(float4 v, float4 m, float4 sc, float4 be, float slope) {
     return make_float4(bn_apply1(v.x, m.x, sc.x, be.x, slope), bn_apply1(v.y, m.y, sc.y, be.y, slope),
                        bn_apply1(v.z, m.z, sc.z, be.z, slope), bn_apply1(v.w, m.w, sc.w, be.w, slope));

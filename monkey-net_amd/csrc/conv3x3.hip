@@ -53,6 +53,20 @@ struct BnBwdSrc {
     float slope;
 };
 
+// The EVALUATION-mode norm layer (+ activation, + 2x2 average pool) behind a forward launch, applied in the launch's own epilogue
+// (sync_batchnorm/batchnorm.py:50-53 with running statistics, behind modules/util.py:63-65,83-88,103-108): the store becomes
+//     z = act_apply(fmaf(v - mean[co], scale[co], beta[co]), slope)        v = the value the plain launch stores (bn_apply1)
+// and the convolution's own output never reaches memory.  mean / scale / beta: what mnk_bn_eval_coeffs makes; slope as in
+// act_apply.  (z, ld_z): where the launch writes -- the launch's y / ld_y are set to the same pair; with pool they describe the
+// (N, H/2, W/2) map and the kernel is a window-major instantiation (row_pixel).  Only the EN != 0 instantiations of the kernels
+// read the record, and only an unsplit launch without residual, statistics and bnb takes one (conv2d_fwd_impl checks).
+struct EvalNorm {
+    const float *mean, *scale, *beta;
+    float slope;
+    float* z;
+    int ld_z;
+};
+
 struct ConvArgs {
     const float* x0;
     const float* x1;
@@ -95,6 +109,9 @@ struct ConvArgs {
     // ---- position-major launches (the PM kernels; conv2d_fwd_impl decides) --------------------------------------------------
     unsigned mulF, shF;     // division of a GEMM row by the frame count N (fast_div)
     unsigned mulKW, shKW;   // division of a tap index by kw
+    // ---- evaluation-mode norm layer in the epilogue (the EN = 1 / 2 kernels); window-major launches (EN = 2) -----------------
+    EvalNorm en;
+    unsigned mulWo, shWo, mulHo, shHo;   // division of a pool-window index by W / 2 and H / 2 (fast_div)
 };
 
 // GEMM row -> output pixel.  Frame-major (the memory order): m = (fr * H + h) * W + w -- 64 consecutive rows of a small map
@@ -102,9 +119,18 @@ struct ConvArgs {
 // the rows of a tile share one position (N >= BM) or BM / N neighbouring ones, and a tap that falls into the padding does so
 // for the whole tile: the block leaves its K steps out (TapCursor).  Only the row <-> pixel map of the launch changes; every
 // tensor, and the split-K workspace [split][phase][M][ldw], keeps its frame-major memory order.
-template <bool PM>
+// Window-major (RM = 2; H, W even): m = ((fr * H/2 + ho) * W/2 + wo) * 4 + 2 dy + dx is pixel (2 ho + dy, 2 wo + dx) -- four
+// consecutive rows are one 2x2 pool window in the pooling kernels' order of additions, and the accumulator layouts keep four
+// consecutive rows of a column in one lane: the epilogue of a launch with an EvalNorm pools in registers and writes row m / 4 of
+// the pooled map (its frame-major order).
+template <int RM>         // 0 frame-major, 1 position-major, 2 window-major (a bool PM converts to 0 / 1)
 __device__ __forceinline__ void row_pixel(const ConvArgs& a, unsigned m, unsigned& fr, unsigned& h, unsigned& w) {
-    if constexpr (PM) {
+    if constexpr (RM == 2) {
+        const unsigned q = m >> 2, tt = fast_div(q, a.mulWo, a.shWo);
+        fr = fast_div(tt, a.mulHo, a.shHo);
+        w = 2u * (q - tt * ((unsigned)a.W >> 1)) + (m & 1u);
+        h = 2u * (tt - fr * ((unsigned)a.H >> 1)) + ((m >> 1) & 1u);
+    } else if constexpr (RM == 1) {
         const unsigned p = fast_div(m, a.mulF, a.shF);
         fr = m - p * (unsigned)a.N;
         h = fast_div(p, a.mulW, a.shW);
@@ -245,8 +271,12 @@ struct ActLoader {
 // PM: the rows are position-major (row_pixel) and the K cursor is `cur`, which the kernel points at the block's first step
 // (TapCursor).  The rows of such a tile lie a whole frame apart, so the buffer window starts at the tensor (the host checks
 // that the sources fit it).
-template <int RA, bool UPS, int NST = 1, bool PM = false>
+// WIN: the rows are window-major (row_pixel): per-row base offsets and out-of-image masks follow the map, the K loop does not
+// care.  A tile's rows are the pool windows from its first one on in frame-major window order, so the lowest pixel row a tile
+// touches is the upper row of its first window.
+template <int RA, bool UPS, int NST = 1, bool PM = false, bool WIN = false>
 struct ActLoader3 {
+    static_assert(!WIN || (!UPS && !PM), "window-major rows: the plain 3x3 loader, frame order of the windows");
     unsigned b0[RA], b1[RA];       // byte offset of the row's centre pixel in source 0 / 1 (relative to the block base)
     unsigned inv[RA];              // bit t: tap t lies outside the image
     unsigned par[RA];              // up-sampling: bit 0 h even, 1 h odd, 2 w even, 3 w odd (bit 4 stays 0)
@@ -269,9 +299,11 @@ struct ActLoader3 {
         Ws = UPS ? a.Wi >> 1 : a.Wi;
         long pbase = 0;            // position-major: the window starts at the tensor
         if constexpr (!PM) {
-            const unsigned mb = (unsigned)(m0 < a.M ? m0 : a.M - 1), tb = fast_div(mb, a.mulW, a.shW),
-                           fb = fast_div(tb, a.mulH, a.shH);
-            const long rowidx0 = (long)fb * Hs + ((int)(tb - fb * (unsigned)a.H) >> (UPS ? 1 : 0));
+            const unsigned mb = (unsigned)(m0 < a.M ? m0 : a.M - 1);
+            unsigned fb, hb, wb;
+            row_pixel<WIN ? 2 : 0>(a, mb, fb, hb, wb);
+            if constexpr (WIN) hb &= ~1u;
+            const long rowidx0 = (long)fb * Hs + ((int)hb >> (UPS ? 1 : 0));
             pbase = rowidx0 * Ws - Ws - 1;
             if (pbase < 0) pbase = 0;
         }
@@ -283,7 +315,7 @@ struct ActLoader3 {
             long ml = m0 + lrow + 64 * j;
             if (ml > a.M - 1) ml = a.M - 1;
             unsigned fr, hu, wu;
-            row_pixel<PM>(a, (unsigned)ml, fr, hu, wu);
+            row_pixel<WIN ? 2 : (PM ? 1 : 0)>(a, (unsigned)ml, fr, hu, wu);
             const int w = (int)wu, h = (int)hu;
             const long rel = ((long)fr * Hs + (h >> (UPS ? 1 : 0))) * Ws + (w >> (UPS ? 1 : 0)) - pbase;
             b0[j] = (unsigned)(rel * a.ld0 * 4);
@@ -456,10 +488,10 @@ struct ActLoaderK {
     __device__ __forceinline__ float4 masked(int j) const { return ra[ST][j]; }
 };
 
-template <int RA, int MODE, int NST = 1, bool PM = false> struct LoaderSel { typedef ActLoader<RA, NST> type; };
-template <int RA, int NST, bool PM> struct LoaderSel<RA, 3, NST, PM> { typedef ActLoaderK<RA, NST, PM> type; };
-template <int RA, int NST, bool PM> struct LoaderSel<RA, 1, NST, PM> { typedef ActLoader3<RA, false, NST, PM> type; };
-template <int RA, int NST, bool PM> struct LoaderSel<RA, 2, NST, PM> { typedef ActLoader3<RA, true, NST, PM> type; };
+template <int RA, int MODE, int NST = 1, bool PM = false, bool WIN = false> struct LoaderSel { typedef ActLoader<RA, NST> type; };
+template <int RA, int NST, bool PM, bool WIN> struct LoaderSel<RA, 3, NST, PM, WIN> { typedef ActLoaderK<RA, NST, PM> type; };
+template <int RA, int NST, bool PM, bool WIN> struct LoaderSel<RA, 1, NST, PM, WIN> { typedef ActLoader3<RA, false, NST, PM, WIN> type; };
+template <int RA, int NST, bool PM, bool WIN> struct LoaderSel<RA, 2, NST, PM, WIN> { typedef ActLoader3<RA, true, NST, PM> type; };
 
 #ifndef MNK_IGEMM_OCC
 #define MNK_IGEMM_OCC 3                       // waves per SIMD = blocks per CU the register budget is held to
@@ -497,9 +529,15 @@ constexpr int LDS_H = 24;     // padded LDS row of the bf16 planes (16 + 8 halve
 // PM: position-major rows + block-uniform tap skipping (row_pixel, TapCursor): fast loaders and fp32 products only, and only
 // launches whose epilogue leaves no per-block column sums -- those are fp32 sums over the rows of a tile, and another row
 // order would change their bits
-template <int BM, int BN, int WM, int WN, int MODE, int GM = 0, bool PM = false>     // MODE: 0 generic loader, 1 / 2 the 3x3 fast loader (plain / x2 up-sampled)
+// EN: the launch has an EvalNorm -- 1: applied per element (any row map; the buffer-load loaders); 2: with the 2x2 average pool, on
+// window-major rows (row_pixel): the plain 3x3 fast loader, and the epilogue writes the pooled map.  A template parameter, not a
+// test of a.en: the training instantiations (EN = 0) stay the code they were (profiles/eval_norm_fused.txt, section 2)
+template <int BM, int BN, int WM, int WN, int MODE, int GM = 0, bool PM = false, int EN = 0>     // MODE: 0 generic loader, 1 / 2 the 3x3 fast loader (plain / x2 up-sampled)
 __global__ void __launch_bounds__(256, MNK_IGEMM_OCC) conv3x3_igemm_kernel(ConvArgs a) {
     static_assert(!PM || (MODE != 0 && GM == 0), "position-major rows: buffer-load loaders, fp32 products");
+    constexpr bool WIN = EN == 2;
+    static_assert(!WIN || (MODE == 1 && !PM), "window-major rows: the plain 3x3 fast loader");
+    static_assert(EN == 0 || MODE != 0, "an EvalNorm launch: buffer-load loaders");
     MNK_PHASE(0);
     constexpr int RA = BM / 64;               // A rows per thread per K step
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
@@ -546,7 +584,7 @@ __global__ void __launch_bounds__(256, MNK_IGEMM_OCC) conv3x3_igemm_kernel(ConvA
 
     // ---- per-thread global->LDS assignment: row inside a 64-row slab, float4 column (4 channels) --------------
     const int lrow = t >> 2, lq = t & 3;
-    typename LoaderSel<RA, MODE, NST, PM>::type L;
+    typename LoaderSel<RA, MODE, NST, PM, WIN>::type L;
     L.setup(a, m0, lrow, lq, s_begin, a.pad - pa, (a.pad_x < 0 ? a.pad : a.pad_x) - pb);
     int n = s_end - s_begin;                  // K steps of this block
     if constexpr (PM) {
@@ -797,17 +835,23 @@ __global__ void __launch_bounds__(256, MNK_IGEMM_OCC) conv3x3_igemm_kernel(ConvA
     int cov[TN];
     float bv[TN], s1[TN], s2[TN];
     const bool bnb = !PM && a.bnb.y != nullptr && a.stats && !split_out;     // the column sums are a BatchNorm layer's backward statistics
+    // an evaluation-mode norm layer applied here (EN; never together with bnb, statistics, a residual or a split): its
+    // per-column coefficients take bnb's registers.  Guarded loads: the coefficients of a pad column are zero
+    constexpr bool en = EN != 0;
+    const float *const cmean = en ? a.en.mean : a.bnb.mean, *const cscale = en ? a.en.scale : a.bnb.scale,
+                *const cbeta = en ? a.en.beta : a.bnb.beta;
+    const float eslope = en ? a.en.slope : -1.f;
     float bm[TN], bis[TN], bsc[TN], bbe[TN];
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         cov[j] = n0 + wn * (BN / WN) + 32 * j + fi;
         bv[j] = (!split_out && a.bias && cov[j] < a.Cout) ? a.bias[cov[j]] : 0.f;
         s1[j] = s2[j] = 0.f;
-        const bool real = bnb && cov[j] < a.Cout;
-        bm[j] = real ? a.bnb.mean[cov[j]] : 0.f;
+        const bool real = bnb && cov[j] < a.Cout, coef = (bnb || en) && cov[j] < a.Cout;
+        bm[j] = coef ? cmean[cov[j]] : 0.f;
         bis[j] = real ? a.bnb.invstd[cov[j]] : 0.f;
-        bsc[j] = real ? a.bnb.scale[cov[j]] : 0.f;
-        bbe[j] = real ? a.bnb.beta[cov[j]] : 0.f;
+        bsc[j] = coef ? cscale[cov[j]] : 0.f;
+        bbe[j] = coef ? cbeta[cov[j]] : 0.f;
     }
     auto emit = [&](auto full_tag) __attribute__((always_inline)) {
         constexpr bool FULL = decltype(full_tag)::value;
@@ -819,6 +863,23 @@ __global__ void __launch_bounds__(256, MNK_IGEMM_OCC) conv3x3_igemm_kernel(ConvA
                 const bool c_real = co < a.Cout, c_store = co < co_lim;
                 const unsigned mb = mrow0 + 32 * i;
                 const unsigned off0 = mb * ldo + (unsigned)co, roff0 = mb * (unsigned)a.ld_res + (unsigned)co;
+                if constexpr (WIN) {
+                    // a lane's register quad 4 g .. 4 g + 3 = rows mb + 8 g .. + 3 = pool window (mb + 8 g) / 4, its pixels in
+                    // bn_apply4_pool's order of additions; v is the plain launch's expression (no residual: + 0)
+                    if (c_store) {
+#pragma unroll
+                        for (int g = 0; g < 4; ++g) {
+                            float o = 0.f;
+#pragma unroll
+                            for (int k = 0; k < 4; ++k)
+                                o += bn_apply1((acc[0][i][j][4 * g + k] + bv[j]) + 0.f, bm[j], bsc[j], bbe[j], eslope);
+                            o *= 0.25f;
+                            const unsigned mw = mb + 8 * g;          // M is a multiple of 4: a window is inside or outside
+                            if (FULL || mw < Mu) obase[(mw >> 2) * ldo + (unsigned)co] = c_real ? o : 0.f;
+                        }
+                    }
+                    continue;
+                }
                 if (c_store) {
                     float rv[16];
 #pragma unroll
@@ -846,6 +907,9 @@ __global__ void __launch_bounds__(256, MNK_IGEMM_OCC) conv3x3_igemm_kernel(ConvA
                         const unsigned ro = (r & 3) + 8 * (r >> 2);
                         float v = acc[0][i][j][r];
                         if (!split_out) v = c_real ? (v + bv[j]) + rv[r] : 0.f;
+                        if constexpr (EN == 1) {
+                            if (c_real) v = bn_apply1(v, bm[j], bsc[j], bbe[j], eslope);          // pad columns stay zero
+                        }
                         if (FULL || mb + ro < Mu) {
                             if (PM || scatter)
                                 obase[out_row(mb + ro) * ldo + (unsigned)co] = v;
@@ -917,8 +981,11 @@ __global__ void __launch_bounds__(256, MNK_IGEMM_OCC) conv3x3_igemm_kernel(ConvA
 // (fi, fk) reads k = 8 fk .. 8 fk + 7 of its row from buffer fk >> 1 -- six MFMAs per 16x16 tile and pair.  Two register stages
 // hold the next pair while the MFMAs of this one run; two barriers per pair.
 // GM = 2: the one-pass form (MNK_CONV_BF16) -- the same pairs with ONE rounded plane per operand and one MFMA per tile and pair.
-template <int BN, int MODE, int GM = 0>
+template <int BN, int MODE, int GM = 0, int EN = 0>       // EN: see conv3x3_igemm_kernel
 __global__ void __launch_bounds__(256) conv3x3_igemm16_kernel(ConvArgs a) {
+    constexpr bool WIN = EN == 2;
+    static_assert(!WIN || MODE == 1, "window-major rows: the plain 3x3 fast loader");
+    static_assert(EN == 0 || MODE != 0, "an EvalNorm launch: buffer-load loaders");
     constexpr int BM = 128, RA = 2, TM = 2, TN = BN / 16;
     constexpr int NSTG = GM ? 2 : 1;
     constexpr int NPL = GM == 2 ? 1 : 3;      // bf16 planes per operand
@@ -940,7 +1007,7 @@ __global__ void __launch_bounds__(256) conv3x3_igemm16_kernel(ConvArgs a) {
     int s_end = s_begin + a.ksteps_per_split;
     if (s_end > a.ksteps) s_end = a.ksteps;
     const int lrow = t >> 2, lq = t & 3;
-    typename LoaderSel<RA, MODE, NSTG>::type L;
+    typename LoaderSel<RA, MODE, NSTG, false, WIN>::type L;
     L.setup(a, m0, lrow, lq, s_begin, a.pad, a.pad_x < 0 ? a.pad : a.pad_x);
     const long KT = (long)a.ksteps * BK;
     const int wco = n0 + (lrow < BN ? lrow : 0);           // rows beyond BN / Cout: clamped, never stored
@@ -1102,6 +1169,10 @@ __global__ void __launch_bounds__(256) conv3x3_igemm16_kernel(ConvArgs a) {
 #pragma unroll
     for (int j = 0; j < TN; ++j) s1[j] = s2[j] = 0.f;
     const bool bnb = a.bnb.y != nullptr && a.stats && !split_out;     // (see BnBwdSrc)
+    constexpr bool en = EN != 0;                                      // (see EvalNorm; the coefficients take bnb's registers)
+    const float *const cmean = en ? a.en.mean : a.bnb.mean, *const cscale = en ? a.en.scale : a.bnb.scale,
+                *const cbeta = en ? a.en.beta : a.bnb.beta;
+    const float eslope = en ? a.en.slope : -1.f;
     auto emit = [&](auto full_tag) __attribute__((always_inline)) {
         constexpr bool FULL = decltype(full_tag)::value;
 #pragma unroll
@@ -1109,14 +1180,23 @@ __global__ void __launch_bounds__(256) conv3x3_igemm16_kernel(ConvArgs a) {
             const int co = n0 + 16 * j + fi;
             const bool c_real = co < a.Cout, c_store = co < co_lim;
             const float bv = (!split_out && a.bias && c_real) ? a.bias[co] : 0.f;
-            const bool breal = bnb && c_real;
-            const float bm = breal ? a.bnb.mean[co] : 0.f, bis = breal ? a.bnb.invstd[co] : 0.f,
-                        bsc = breal ? a.bnb.scale[co] : 0.f, bbe = breal ? a.bnb.beta[co] : 0.f;
+            const bool breal = bnb && c_real, coef = (bnb || en) && c_real;
+            const float bm = coef ? cmean[co] : 0.f, bis = breal ? a.bnb.invstd[co] : 0.f,
+                        bsc = coef ? cscale[co] : 0.f, bbe = coef ? cbeta[co] : 0.f;
             if (c_store) {
 #pragma unroll
                 for (int i = 0; i < TM; ++i) {
                     const unsigned mb = mrow0 + 16 * i;
                     const unsigned off0 = mb * ldo + (unsigned)co, roff0 = mb * (unsigned)a.ld_res + (unsigned)co;
+                    if constexpr (WIN) {
+                        // the lane's four registers = rows mb .. mb + 3 = pool window mb / 4 (see the 32x32-tile kernel)
+                        float o = 0.f;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) o += bn_apply1((acc[i][j][r] + bv) + 0.f, bm, bsc, bbe, eslope);
+                        o *= 0.25f;
+                        if (FULL || mb < Mu) obase[(mb >> 2) * ldo + (unsigned)co] = c_real ? o : 0.f;
+                        continue;
+                    }
                     float rv[4] = {0.f, 0.f, 0.f, 0.f}, yv[4] = {0.f, 0.f, 0.f, 0.f};
                     if (use_res && c_real) {
 #pragma unroll
@@ -1133,6 +1213,9 @@ __global__ void __launch_bounds__(256) conv3x3_igemm16_kernel(ConvArgs a) {
                     for (int r = 0; r < 4; ++r) {
                         float v = acc[i][j][r];
                         if (!split_out) v = c_real ? (v + bv) + rv[r] : 0.f;
+                        if constexpr (EN == 1) {
+                            if (c_real) v = bn_apply1(v, bm, bsc, bbe, eslope);                   // pad columns stay zero
+                        }
                         if (FULL || mb + r < Mu) {
                             obase[off0 + r * ldo] = v;
                             if (bnb) {
@@ -1771,6 +1854,36 @@ static bool plan_taps(const Plan& p, int mode, bool one_pass, bool column_sums, 
     return true;
 }
 
+// The activation-side loader of a forward / data-gradient launch (LoaderSel): 1 / 2 -- the 3x3 / pad 1 fast form (plain / through
+// the x2 up-sampled view) when the caller vouches for clean pad channels and a block's pixel span fits the 2^30-byte buffer
+// window (always, short of ~2 M-float pixel rows); 3 -- any other K x K / pad (the discriminator's 4x4 convolutions and their
+// pad-3 data gradients, the sub-pixel forms): ActLoaderK.  A block's 128 output pixels span at most 128 * kh * kw + (kh + 3) * Wi
+// input pixels (a 1x1 output per frame advances a whole kh x kw input frame per output pixel; plus the rows of the taps);
+// 0 -- the generic loader.  ldmax: the larger leading dimension of the sources; aligned: both sources start on 16 bytes.
+static long kxk_span_bytes(int kh, int kw, int stride, int Wi, int ldmax) {
+    return (128L * kh * kw * stride * stride + (long)(kh + 3) * Wi) * ldmax * 4;
+}
+static int loader_mode(bool clean, int ups, int kh, int kw, int pad, int stride, int phases, int Wi, int ldmax, bool aligned) {
+    const long span = ((long)BK * 8 + 3L * (ups ? Wi / 2 : Wi) + 8) * ldmax * 4;
+    if (g_fast_loader && clean && kh == 3 && kw == 3 && pad == 1 && stride == 1 && phases == 1 && span < (1L << 29) && aligned)
+        return ups ? 2 : 1;
+    if (g_fast_loader && g_kxk_fast && clean && !ups && kh * kw <= 32 && pad >= 0 && pad < kh && pad < kw &&
+        kxk_span_bytes(kh, kw, stride, Wi, ldmax) < (1L << 29) && aligned)
+        return 3;
+    return 0;
+}
+
+// How a forward launch with an EvalNorm runs (mnk_conv3x3_evalnorm_form): 0 -- it cannot (the plan splits K; the generic loader;
+// a pooled layer whose launch has no window-major kernel: another loader than the plain 3x3 fast one, or a position-major plan,
+// whose blocks would lose their tap skipping); 1 -- per element; 2 -- with the pool.  A window-major tile of 128 rows spans at most
+// 128 + 7 W pixels of its source (32 windows of one or more window rows, each two pixel rows, plus the taps' halo).
+static int evalnorm_form_of(const Plan& p, int mode, bool pm, int pool, int Wi, int ldmax) {
+    if (p.splits > 1 || mode == 0) return 0;        // (the generic loader -- sources without clean pads -- has no such kernel)
+    if (!pool) return (p.bn == 16 || p.bn == 48) && mode == 3 ? 0 : 1;
+    return (mode == 1 && !pm && ((long)BK * 8 + 8L * Wi + 8) * ldmax * 4 < (1L << 29)) ? 2 : 0;
+}
+static int g_last_evalnorm_form = 0;     // of the last forward / data-gradient launch (0: a plain launch)
+
 }  // namespace
 
 extern "C" {
@@ -1850,6 +1963,7 @@ struct IgemmLaunch {
     bool timed;               // the roofline kernel is timed by its own begin / end stamps
     hipEvent_t ev0, ev1;
     bool pm;                  // the position-major, tap-skipping instantiation (plan_taps)
+    int en;                   // the EvalNorm instantiation: 0 none, 1 per element (loader modes 1 .. 3), 2 pooled (loader mode 1)
 };
 static void launch_igemm(void (*kernel)(ConvArgs), const IgemmLaunch& L, const ConvArgs& a) {
     if (L.timed) hipExtLaunchKernelGGL(kernel, L.grid, dim3(256), 0, L.s, L.ev0, L.ev1, 0, a);
@@ -1858,6 +1972,20 @@ static void launch_igemm(void (*kernel)(ConvArgs), const IgemmLaunch& L, const C
 // the 32x32-MFMA kernel of a tile / the 16x16-MFMA kernel of a width, by loader mode; GM: 1 = bf16x3 products, 2 = one-pass bf16
 template <int BM, int BN, int WM, int WN, int GM>
 static void launch_tile(int mode, const IgemmLaunch& L, const ConvArgs& a) {
+    if (L.en == 1) {      // per element (evalnorm_form_of vouches for mode 1 .. 3)
+        if constexpr (GM == 0) {
+            if (L.pm) {
+                if (mode == 1) launch_igemm(conv3x3_igemm_kernel<BM, BN, WM, WN, 1, 0, true, 1>, L, a);
+                else if (mode == 2) launch_igemm(conv3x3_igemm_kernel<BM, BN, WM, WN, 2, 0, true, 1>, L, a);
+                else launch_igemm(conv3x3_igemm_kernel<BM, BN, WM, WN, 3, 0, true, 1>, L, a);
+                return;
+            }
+        }
+        if (mode == 1) launch_igemm(conv3x3_igemm_kernel<BM, BN, WM, WN, 1, GM, false, 1>, L, a);
+        else if (mode == 2) launch_igemm(conv3x3_igemm_kernel<BM, BN, WM, WN, 2, GM, false, 1>, L, a);
+        else launch_igemm(conv3x3_igemm_kernel<BM, BN, WM, WN, 3, GM, false, 1>, L, a);
+        return;
+    }
     if constexpr (GM == 0) {
         if (L.pm) {       // position-major rows + tap skipping (plan_taps vouches for mode 1 .. 3)
             if (mode == 1) launch_igemm(conv3x3_igemm_kernel<BM, BN, WM, WN, 1, 0, true>, L, a);
@@ -1873,13 +2001,30 @@ static void launch_tile(int mode, const IgemmLaunch& L, const ConvArgs& a) {
 }
 template <int BN, int GM>
 static void launch_tile16(int mode, const IgemmLaunch& L, const ConvArgs& a) {
+    if (L.en == 1) {      // per element: 3x3 / pad 1 launches only (plan_tile_ok: phases == 1), loader mode 1 or 2
+        if (mode == 1) launch_igemm(conv3x3_igemm16_kernel<BN, 1, GM, 1>, L, a);
+        else launch_igemm(conv3x3_igemm16_kernel<BN, 2, GM, 1>, L, a);
+        return;
+    }
     if (mode == 1) launch_igemm(conv3x3_igemm16_kernel<BN, 1, GM>, L, a);
     else if (mode == 2) launch_igemm(conv3x3_igemm16_kernel<BN, 2, GM>, L, a);
     else if (mode == 3) launch_igemm(conv3x3_igemm16_kernel<BN, 3, GM>, L, a);
     else launch_igemm(conv3x3_igemm16_kernel<BN, 0, GM>, L, a);
 }
+// the window-major kernels: every tile of plan_tile_ok, the plain 3x3 fast loader
+template <int GM>
+static void launch_plan_tile_win(const Plan& p, const IgemmLaunch& L, const ConvArgs& a) {
+    if (p.bn == 16) launch_igemm(conv3x3_igemm16_kernel<16, 1, GM, 2>, L, a);
+    else if (p.bn == 48) launch_igemm(conv3x3_igemm16_kernel<48, 1, GM, 2>, L, a);
+    else if (p.bn == 128 && p.bm == 128) launch_igemm(conv3x3_igemm_kernel<128, 128, 2, 2, 1, GM, false, 2>, L, a);
+    else if (p.bn == 128) launch_igemm(conv3x3_igemm_kernel<64, 128, 1, 4, 1, GM, false, 2>, L, a);
+    else if (p.bn == 64 && p.bm == 128) launch_igemm(conv3x3_igemm_kernel<128, 64, 2, 2, 1, GM, false, 2>, L, a);
+    else if (p.bn == 64) launch_igemm(conv3x3_igemm_kernel<64, 64, 2, 2, 1, GM, false, 2>, L, a);
+    else launch_igemm(conv3x3_igemm_kernel<128, 32, 4, 1, 1, GM, false, 2>, L, a);
+}
 template <int GM>
 static void launch_plan_tile(const Plan& p, int mode, const IgemmLaunch& L, const ConvArgs& a) {
+    if (L.en == 2) return launch_plan_tile_win<GM>(p, L, a);
     if (p.bn == 16) launch_tile16<16, GM>(mode, L, a);
     else if (p.bn == 48) launch_tile16<48, GM>(mode, L, a);
     else if (p.bn == 128 && p.bm == 128) launch_tile<128, 128, 2, 2, GM>(mode, L, a);
@@ -1896,8 +2041,13 @@ static void launch_plan_tile(const Plan& p, int mode, const IgemmLaunch& L, cons
 static int conv2d_fwd_impl(const float* x0, int ld0, int C0, const float* x1, int ld1, int C1, int flags, int Hi, int Wi, int kh,
                            int kw, int pad, int stride, int phases, const float* wp, const float* bias, const float* residual,
                            int ld_res, float* y, int ld_y, int N, int Ho, int Wo, int Cout, float* ws, size_t ws_floats,
-                           float* stats_partial, void* stream, const BnBwdSrc* bnb = nullptr) {
+                           float* stats_partial, void* stream, const BnBwdSrc* bnb = nullptr, const EvalNorm* en = nullptr,
+                           int pool = 0) {
+    // en: the evaluation-mode norm layer applied in the epilogue; (y, ld_y) is then where z goes -- with pool the (N, Ho/2, Wo/2) map
     MNK_REQUIRE(flags >= 0 && flags <= 31);
+    MNK_REQUIRE(!en || (en->mean && en->scale && en->beta && !residual && !stats_partial && !bnb &&
+                        !(flags & (MNK_CONV_DEFER_SPLITK | MNK_CONV_BF16_TRAIN))));
+    MNK_REQUIRE(!pool || (en && phases == 1 && kh == 3 && kw == 3 && pad == 1 && stride == 1 && Ho % 2 == 0 && Wo % 2 == 0));
     const int ups = flags & MNK_CONV_UPSAMPLED, clean = (flags & MNK_CONV_CLEAN_PADS) ? 1 : 0;
     // MNK_CONV_BF16 / MNK_CONV_BF16_TRAIN: the one-pass bf16 products (GM = 2) -- a property of this launch; tile and split are
     // those of the fp32 plan.  MNK_CONV_BF16 is the inference request: the column sums of the epilogue are a training request and
@@ -1966,11 +2116,20 @@ static int conv2d_fwd_impl(const float* x0, int ld0, int C0, const float* x1, in
     a.ldw = p.ldw;
     a.stats = stats_partial;
     a.bnb = bnb ? *bnb : BnBwdSrc{};
+    a.en = en ? *en : EvalNorm{};
+    a.en.z = y, a.en.ld_z = ld_y;
+    fast_div_consts((unsigned)(Wo > 1 ? Wo / 2 : 1), &a.mulWo, &a.shWo);
+    fast_div_consts((unsigned)(Ho > 1 ? Ho / 2 : 1), &a.mulHo, &a.shHo);
     MNK_REQUIRE(!bnb || (stats_partial && bnb->y && bnb->mean && bnb->invstd && bnb->scale && bnb->beta && bnb->ld >= Cout &&
                          phases == 1 && !defer_splitk));
     a.xcd = g_xcd_remap;
     // statistics: only where the query answers > 0, and not from partials that are left to the caller
     MNK_REQUIRE(!stats_partial || (ld_y == round_up(Cout, 4) && l.stats_floats && (p.splits == 1 || !defer_splitk)));
+    if (en && p.splits > 1) {      // (in front of the workspace check: such a launch has no workspace to offer)
+        set_error("a convolution with the evaluation-mode norm layer in its epilogue is not possible at this shape and tuning "
+                  "(mnk_conv3x3_evalnorm_form answers 0: the plan splits K %d times)", p.splits);
+        return MNK_EINVAL;
+    }
     if (l.ws_floats && (!ws || ws_floats < l.ws_floats)) {
         set_error("mnk_conv2d_fwd: workspace too small (%zu < %zu floats)", ws_floats, l.ws_floats);
         return MNK_EWORKSPACE;
@@ -1983,21 +2142,12 @@ static int conv2d_fwd_impl(const float* x0, int ld0, int C0, const float* x1, in
         const double alg = phases == 4 ? 2.0 * 4.0 * (double)a.M * Cout * 9.0 * (C0 + C1)
                                        : (stride == 2 ? 2.0 * 4.0 * (double)a.M * Cout * 9.0 * (C0 + C1)
                                                       : 2.0 * (double)a.M * Cout * (double)ntaps * (C0 + C1));
-        // loader: the 3x3 / pad 1 fast form when the caller vouches for clean pad channels and a block's pixel span
-        // fits the 2^30-byte buffer window (always, short of ~2 M-float pixel rows)
-        const long span = ((long)BK * 8 + 3L * (ups ? Wi / 2 : Wi) + 8) * (ld0 > ld1 ? ld0 : ld1) * 4;
-        int mode = (g_fast_loader && a.clean && kh == 3 && kw == 3 && pad == 1 && stride == 1 && phases == 1 &&
-                    span < (1L << 29) && (size_t)x0 % 16 == 0 && (!x1 || (size_t)x1 % 16 == 0)) ? (ups ? 2 : 1) : 0;
-        // any other K x K / pad (the discriminator's 4x4 convolutions and their pad-3 data gradients): ActLoaderK.  A
-        // block's 128 output pixels span at most 128 * kh * kw + (kh + 3) * Wi input pixels (a 1x1 output per frame
-        // advances a whole kh x kw input frame per output pixel; plus the rows of the taps)
-        const long span_k = (128L * kh * kw * stride * stride + (long)(kh + 3) * Wi) * (ld0 > ld1 ? ld0 : ld1) * 4;
+        const int ldmax = ld0 > ld1 ? ld0 : ld1;
+        const bool aligned = (size_t)x0 % 16 == 0 && (!x1 || (size_t)x1 % 16 == 0);
+        const int mode = loader_mode(a.clean, ups, kh, kw, pad, stride, phases, Wi, ldmax, aligned);
         MNK_REQUIRE((stride == 1 && phases == 1) ||
-                    (g_fast_loader && g_kxk_fast && ntaps <= 32 && span_k < (1L << 29) && (size_t)x0 % 16 == 0 &&
-                     (!x1 || (size_t)x1 % 16 == 0)));          // strided / sub-pixel forms exist for the K x K buffer loader only
-        if (mode == 0 && g_fast_loader && g_kxk_fast && a.clean && !ups && ntaps <= 32 && pad >= 0 && pad < kh && pad < kw &&
-            span_k < (1L << 29) && (size_t)x0 % 16 == 0 && (!x1 || (size_t)x1 % 16 == 0))
-            mode = 3;
+                    (g_fast_loader && g_kxk_fast && ntaps <= 32 && kxk_span_bytes(kh, kw, stride, Wi, ldmax) < (1L << 29) &&
+                     aligned));                                // strided / sub-pixel forms exist for the K x K buffer loader only
         // position-major rows where that lets blocks skip the K steps of taps that only read padding (plan_taps)
         const TapGeom tg = {p.bm, N, Ho, Wo, Hi, Wi, kh, kw, pad, stride, phases};
         const long src_pixels = (long)N * (ups ? Hi / 2 : Hi) * (ups ? Wi / 2 : Wi);
@@ -2005,6 +2155,15 @@ static int conv2d_fwd_impl(const float* x0, int ld0, int C0, const float* x1, in
         const bool pm = plan_taps(p, mode, one_pass, stats_partial && p.splits == 1, tg, src_pixels * (ld0 > ld1 ? ld0 : ld1) * 4, &row_taps);
         fast_div_consts((unsigned)N, &a.mulF, &a.shF);
         fast_div_consts((unsigned)kw, &a.mulKW, &a.shKW);
+        // a launch that applies the norm layer behind it: refused where the form query answers 0, never computed another way
+        const int en_form = en ? evalnorm_form_of(p, mode, pm, pool, Wi, ldmax) : 0;
+        if (en && !en_form) {
+            set_error("a convolution with the evaluation-mode norm layer in its epilogue is not possible at this shape and tuning "
+                      "(mnk_conv3x3_evalnorm_form answers 0: loader %d, %s rows%s)", mode, pm ? "position-major" : "frame-major",
+                      pool ? ", pooled" : "");
+            return MNK_EINVAL;
+        }
+        g_last_evalnorm_form = en_form;
         // what the launch issues: the sub-pixel forms run 4 (forward) / 16 at a quarter of the pixels (data gradient) taps; a
         // position-major launch only the (row, tap) pairs of the taps its tiles do not skip
         ProfScope prof(K_CONV_FWD, s, alg, 2.0 * row_taps * Cout * (double)(C0 + C1));
@@ -2014,7 +2173,7 @@ static int conv2d_fwd_impl(const float* x0, int ld0, int C0, const float* x1, in
         // (padding a block's LDS request so that exactly ceil(blocks / CUs) blocks fit a CU was built and measured in round 4: the
         // dispatcher already puts 1024 blocks on 256 CUs four by four -- tools/microbench/launch_gap.hip (e) -- and the step did
         // not move, 10.33 vs 10.32 ms: removed.  profiles/r04_knob_ab_log.txt)
-        const IgemmLaunch L = {grid, s, timed, ev0, ev1, pm};
+        const IgemmLaunch L = {grid, s, timed, ev0, ev1, pm, en_form};
         if (one_pass) launch_plan_tile<2>(p, mode, L, a);
         else if (p.bn == 16 || p.bn == 48 ? g_gemm16_bf16x3 : g_gemm_bf16x3) launch_plan_tile<1>(p, mode, L, a);
         else launch_plan_tile<0>(p, mode, L, a);
@@ -2185,6 +2344,51 @@ int mnk_conv3x3_fwd(const float* x0, int ld0, int C0, const float* x1, int ld1, 
                     int Cout, float* ws, size_t ws_floats, float* stats_partial, void* stream) {
     return mnk_conv2d_fwd(x0, ld0, C0, x1, ld1, C1, flags, H, W, 3, 3, 1, wp, bias, residual, ld_res, y, ld_y, N, H, W, Cout,
                           ws, ws_floats, stats_partial, stream);
+}
+
+// ---- forward launches that apply the evaluation-mode norm layer behind them (EvalNorm) ------------------------------------------
+// what the launch entries below will do at this shape under the current tuning: 0 refuse, 1 per element, 2 with the pool.  The
+// query assumes what the library's own activations have: sources on 16-byte boundaries with leading dimension round_up(C, 4)
+int mnk_conv3x3_evalnorm_form(int N, int H, int W, int C0, int C1, int Cout, int flags, int up, int pool) {
+    if (N <= 0 || H <= 0 || W <= 0 || C0 <= 0 || C1 < 0 || Cout <= 0 || flags < 0 || flags > 31) return 0;
+    if (flags & (MNK_CONV_DEFER_SPLITK | MNK_CONV_BF16_TRAIN)) return 0;
+    if (up && (pool || (flags & ~MNK_CONV_BF16))) return 0;
+    if (pool && (H % 2 || W % 2)) return 0;
+    const int ups = up ? 0 : (flags & MNK_CONV_UPSAMPLED), kk = up ? 2 : 3, phases = up ? 4 : 1;
+    if (ups && (H % 2 || W % 2)) return 0;
+    const Launch l = plan_launch(kk * kk, phases, N, H, W, C0, C1, Cout);
+    const int ldmax = round_up(C0 > C1 ? C0 : C1, 4);
+    const int mode = loader_mode(up || (flags & MNK_CONV_CLEAN_PADS), ups, kk, kk, 1, 1, phases, W, ldmax, true);
+    if (up && mode != 3) return 0;           // the sub-pixel form exists for the K x K buffer loader only
+    const TapGeom tg = {l.p.bm, N, H, W, H, W, kk, kk, 1, 1, phases};
+    const long src_pixels = (long)N * (ups ? H / 2 : H) * (ups ? W / 2 : W);
+    double row_taps;
+    const bool pm = plan_taps(l.p, mode, (flags & MNK_CONV_BF16) != 0, false, tg, src_pixels * ldmax * 4, &row_taps);
+    return evalnorm_form_of(l.p, mode, pm, pool, W, ldmax);
+}
+// the form of the last forward launch: 0 a plain launch, 1 / 2 as above (tests: what the query promised is what ran)
+int mnk_conv3x3_last_evalnorm_form(void) { return g_last_evalnorm_form; }
+
+static EvalNorm evalnorm_of(const float* mean, const float* scale, const float* beta, int relu) {
+    EvalNorm e;
+    e.mean = mean, e.scale = scale, e.beta = beta, e.slope = relu ? 0.f : -1.f, e.z = nullptr, e.ld_z = 0;
+    return e;
+}
+int mnk_conv3x3_fwd_evalnorm(const float* x0, int ld0, int C0, const float* x1, int ld1, int C1, int flags, const float* wp,
+                             const float* bias, const float* mean, const float* scale, const float* beta, int relu, int pool,
+                             float* z, int ld_z, int N, int H, int W, int Cout, void* stream) {
+    MNK_REQUIRE(mean && scale && beta && z && (flags & ~(MNK_CONV_UPSAMPLED | MNK_CONV_CLEAN_PADS | MNK_CONV_BF16)) == 0);
+    const EvalNorm e = evalnorm_of(mean, scale, beta, relu);
+    return conv2d_fwd_impl(x0, ld0, C0, x1, ld1, C1, flags, H, W, 3, 3, 1, 1, 1, wp, bias, nullptr, 0, z, ld_z, N, H, W, Cout, nullptr,
+                           0, nullptr, stream, nullptr, &e, pool ? 1 : 0);
+}
+int mnk_conv3x3_up_fwd_evalnorm(const float* x0, int ld0, int C0, const float* x1, int ld1, int C1, int flags, const float* wp_up,
+                                const float* bias, const float* mean, const float* scale, const float* beta, int relu, float* z,
+                                int ld_z, int N, int H, int W, int Cout, void* stream) {
+    MNK_REQUIRE(mean && scale && beta && z && (flags & ~MNK_CONV_BF16) == 0);
+    const EvalNorm e = evalnorm_of(mean, scale, beta, relu);
+    return conv2d_fwd_impl(x0, ld0, C0, x1, ld1, C1, MNK_CONV_CLEAN_PADS | flags, H, W, 2, 2, 1, 1, 4, wp_up, bias, nullptr, 0, z, ld_z,
+                           N, H, W, Cout, nullptr, 0, nullptr, stream, nullptr, &e, 0);
 }
 }
 

@@ -203,3 +203,14 @@ __device__ __forceinline__ float block_max_256(float v, float* red) {
     __syncthreads();
     return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
+
+// activation behind a norm layer.  slope < 0: identity; 0: ReLU; > 0: LeakyReLU
+__device__ __forceinline__ float act_apply(float v, float slope) {
+    return (slope >= 0.f && !(v > 0.f)) ? v * slope : v;
+}
+// z = act((y - mean) * scale + beta) -- THE apply formula of every forward form of the norm layers (batchnorm.hip) and of the
+// convolution epilogues that apply an evaluation-mode norm layer themselves (conv3x3.hip, EvalNorm): one expression, so the
+// forms agree bit for bit
+__device__ __forceinline__ float bn_apply1(float v, float m, float sc, float be, float slope) {
+    return act_apply(fmaf(v - m, sc, be), slope);
+}

@@ -465,7 +465,7 @@ class EvalRunner:
     calls).  Re-captured when a parameter, a buffer or the optimiser epoch changed (load_state_dict between two videos).
     The forward is captured inside ops.inference_precision(eval_precision()) -- an enclosing bf16 scope, else MNK_EVAL_PRECISION;
     the precision is part of the program key, so a changed scope or variable captures a program of its own instead of replaying
-    the other form."""
+    the other form.  The same holds for ops.eval_norm_fusion(eval_fuse_norm()): an enclosing scope, else MNK_EVAL_FUSE_NORM."""
 
     MAX_PROGRAMS = 8
 
@@ -506,14 +506,14 @@ class EvalRunner:
         key = self._flatten((inputs, kwargs), flat)
         if not flat or any(t.dtype != torch.float32 for _, t in flat):
             return NotImplemented
-        precision = eval_precision()
-        key = (precision, key)
+        precision, fuse = eval_precision(), eval_fuse_norm()
+        key = (precision, fuse, key)
         fp = self._fingerprint(module)
         prog = self.programs.get(key)
         if prog is None or prog["fp"] != fp:
             if len(self.programs) >= self.MAX_PROGRAMS:
                 self.programs.clear()
-            prog = self.programs[key] = self._capture(module, inputs, kwargs, flat, device, fp, precision)
+            prog = self.programs[key] = self._capture(module, inputs, kwargs, flat, device, fp, precision, fuse)
         dsts, srcs = [], []
         for i, ((path, t), s) in enumerate(zip(flat, prog["static"])):
             if t.device.type == "cpu" and not t.is_pinned():
@@ -551,21 +551,22 @@ class EvalRunner:
         ring["buf"][k].copy_(t)
         return ring["buf"][k], ring["ev"][k]
 
-    def _capture(self, module, inputs, kwargs, flat, device, fp, precision="fp32"):
+    def _capture(self, module, inputs, kwargs, flat, device, fp, precision="fp32", fuse=False):
         static = [t.to(device).clone() for _, t in flat]
         leaves = {path: s for (path, _), s in zip(flat, static)}
         s_in, s_kw = self._rebuild((inputs, kwargs), leaves)
         cap = torch.cuda.Stream()
         cap.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(cap), mops.inference_precision(precision):     # the caches are keyed by stream: fill them on the
-            for _ in range(2):                                               # stream the capture runs on
+        # (the caches are keyed by stream: fill them on the stream the capture runs on)
+        with torch.cuda.stream(cap), mops.inference_precision(precision), mops.eval_norm_fusion(fuse):
+            for _ in range(2):
                 module(*s_in, **s_kw)
         torch.cuda.current_stream().wait_stream(cap)
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
         mops.FROZEN_CAPTURE[0] = True
         try:
-            with torch.cuda.graph(graph, stream=cap), mops.inference_precision(precision):
+            with torch.cuda.graph(graph, stream=cap), mops.inference_precision(precision), mops.eval_norm_fusion(fuse):
                 out = module(*s_in, **s_kw)
         finally:
             mops.FROZEN_CAPTURE[0] = False
@@ -600,6 +601,12 @@ def eval_precision():
     The captured program and the eager fall-backs (MNK_EVAL_GRAPH=0, a signature the runner declines) both use it."""
     scope = mops.current_precision()
     return scope if scope != "fp32" else mops.check_precision(knobs.get("MNK_EVAL_PRECISION"))
+
+
+def eval_fuse_norm():
+    """whether an evaluation-mode forward behind DataParallelWithCallback runs inside ops.eval_norm_fusion: an enclosing scope that
+    is on, else MNK_EVAL_FUSE_NORM.  Like eval_precision it is part of the captured program's key and the eager fall-backs use it."""
+    return bool(mops.current_norm_fusion() or knobs.on("MNK_EVAL_FUSE_NORM"))
 
 
 def eval_runner_for(wrapper):

@@ -563,11 +563,15 @@ class Reconstructor:
     hipGraph and replayed per batch (BASELINE config 5: "hipGraph-captured generator forward").  The returned tensors of
     the graph form are static buffers that the next call overwrites: clone what must survive.
     precision: "fp32", or "bf16" -- the forward runs inside ops.inference_precision(precision): the 3x3 convolutions round their
-    operands to bf16 ("bf16 inference").  A captured graph keeps the precision it was built with."""
+    operands to bf16 ("bf16 inference").  A captured graph keeps the precision it was built with.
+    fuse_norm: the forward runs inside ops.eval_norm_fusion(fuse_norm): unsplit convolutions apply the evaluation-mode norm
+    layer, ReLU and pool behind them in their own epilogue; the outputs are equal to the default's.  A
+    captured graph keeps the form it was built with."""
 
-    def __init__(self, kp_detector, generator, use_graph=False, precision="fp32"):
+    def __init__(self, kp_detector, generator, use_graph=False, precision="fp32", fuse_norm=False):
         self.kp_detector, self.generator = kp_detector.eval(), generator.eval()
         self.precision = mops.check_precision(precision)
+        self.fuse_norm = bool(fuse_norm)
         self.use_graph = bool(use_graph)
         self._graph = None
         self._static_in = None
@@ -575,7 +579,7 @@ class Reconstructor:
 
     @torch.no_grad()
     def _forward(self, source, driving):
-        with mops.inference_precision(self.precision):
+        with mops.inference_precision(self.precision), mops.eval_norm_fusion(self.fuse_norm):
             kp_source = self.kp_detector(source)
             kp_driving = self.kp_detector(driving)
             out = self.generator(source, kp_driving=kp_driving, kp_source=kp_source)
@@ -648,16 +652,18 @@ class Transfer:
     Returns the dict transfer_one returns.  shared_source=True hands the generator the B source images and the (B, d)
     key points as they are: the appearance encoder runs once per source instead of once per frame, and its skip tensors
     exist once (B instead of B*d rows); False repeats the source d times along the batch axis.
-    precision: "fp32" or "bf16", the ops.inference_precision scope the call runs in (see Reconstructor)."""
+    precision: "fp32" or "bf16", the ops.inference_precision scope the call runs in (see Reconstructor); fuse_norm: the
+    ops.eval_norm_fusion scope it runs in (see Reconstructor)."""
 
-    def __init__(self, kp_detector, generator, normalization_params, shared_source=False, precision="fp32"):
+    def __init__(self, kp_detector, generator, normalization_params, shared_source=False, precision="fp32", fuse_norm=False):
         self.kp_detector, self.generator = kp_detector.eval(), generator.eval()
         self.precision = mops.check_precision(precision)
+        self.fuse_norm = bool(fuse_norm)
         self.params = dict(normalization_params)
         self.shared_source = bool(shared_source)
 
     def __call__(self, source_image, driving_video):
-        with torch.no_grad(), mops.inference_precision(self.precision):
+        with torch.no_grad(), mops.inference_precision(self.precision), mops.eval_norm_fusion(self.fuse_norm):
             return self._run(source_image, driving_video)
 
     def _run(self, source_image, driving_video):

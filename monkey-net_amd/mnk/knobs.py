@@ -39,6 +39,10 @@ KNOBS = {
                                    "(mnk.ops.inference_precision; INTEGRATION.md).  Part of the captured program's key: changing the "
                                    "variable re-captures instead of replaying the other form.  An enclosing bf16 "
                                    "inference_precision scope takes precedence; the wrapper's eager fall-backs use the same value"),
+    "MNK_EVAL_FUSE_NORM": ("0", "1: the evaluation-mode forward that mnk.dropin.EvalRunner captures (and the wrapper's eager "
+                                "fall-backs) runs inside mnk.ops.eval_norm_fusion: unsplit 3x3 convolutions apply the norm layer, ReLU "
+                                "and pool behind them in their own epilogue; same outputs (INTEGRATION.md 2e).  Part of the captured "
+                                "program's key: changing the variable re-captures.  An enclosing scope that is on takes precedence"),
     "MNK_TRAIN_PRECISION": ("fp32", "the training iteration that mnk.dropin.TrainPairRunner serves behind the reference's own train.py: "
                                     "fp32, or bf16 = the 3x3 convolutions run forward, data gradient and weight gradient on "
                                     "bf16-rounded operands with fp32 accumulation (mnk.ops.training_precision; INTEGRATION.md 2d).  Part "

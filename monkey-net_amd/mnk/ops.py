@@ -898,6 +898,7 @@ def handover_state():
     _DZ_STATS: entries die with their tensors or at clear_dz_stats().)"""
     slots = {
         "_SPLIT_PENDING (split-K convolution -> the norm layer that sums its partials)": len(_SPLIT_PENDING),
+        "_FUSED_PENDING (convolution that applied its norm layer -> the bn_act that hands z through)": len(_FUSED_PENDING),
         "_LAST_BN (BNActFn.forward -> bn_act)": _LAST_BN[0],
         "_DY_SUMS (BNActFn.backward -> Conv3x3Fn.backward)": _DY_SUMS[0],
         "_SKIP_PARAM_GRADS (no_param_grads)": _SKIP_PARAM_GRADS[0],
@@ -1054,12 +1055,96 @@ class Conv3x3SkipFn(_Fn):
         return Conv3x3Fn._backward(ctx, dy, dskip)
 
 
-def conv3x3(x0, c0, weight, bias=None, x1=None, c1=0, ups=False, residual=None, want_stats=False, skip=False, eval_bn=False):
+# ---- opt-in evaluation-mode norm fusion --------------------------------------------------------------------------------------
+# In evaluation mode the norm layer behind a convolution is a constant per-channel affine.  Inside `eval_norm_fusion(True)` an
+# UNSPLIT 3x3 / sub-pixel forward launched under torch.no_grad() for a caller that vouches for its norm layer (conv3x3(eval_bn=True,
+# follow=(norm, relu, pool))) applies that layer, its ReLU and (DownBlock3D) the 2x2 average pool in its own epilogue
+# (mnk_conv3x3_fwd_evalnorm / mnk_conv3x3_up_fwd_evalnorm): z is written once and y never.  Equal to the two launches bit for bit.
+# Where the library's form query answers 0 -- a split plan (the deferred-split hand-over serves it), a pooled layer without a
+# window-major kernel -- and in training, with gradients enabled or with the scope off, everything is what it was.
+_FUSE_NORM = [False]
+# the finished output of a fused launch on its way to the bn_act that the caller runs next: z.data_ptr() -> (z, norm, relu, pool)
+_FUSED_PENDING = {}
+# conv -> evaluation-mode norm pairs (callers that pass `follow`) under no_grad since clear_eval_norm_count():
+# [fused per element, fused with the pool, deferred split-K (mnk_bn_eval_split_fwd), separate launches]
+EVAL_NORM_COUNT = [0, 0, 0, 0]
+_PAIR_PENDING = [None]                    # y.data_ptr() of an unfused pair's convolution, for the count in bn_act
+
+
+class eval_norm_fusion:
+    """Context manager: `with eval_norm_fusion(True):` (see above).  One value per process, like inference_precision; the previous
+    value is restored on exit, also after an exception."""
+
+    def __init__(self, on=True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.previous = _FUSE_NORM[0]
+        _FUSE_NORM[0] = self.on
+        return self
+
+    def __exit__(self, *exc):
+        _FUSE_NORM[0] = self.previous
+        return False
+
+
+def current_norm_fusion():
+    return _FUSE_NORM[0]
+
+
+def clear_eval_norm_count():
+    EVAL_NORM_COUNT[:] = [0, 0, 0, 0]
+
+
+def _conv_evalnorm(x0, c0, x1, c1, ups, weight, bias, norm, relu, pool):
+    """conv3x3's fused evaluation form: -> z = pool(act(norm(conv))) from one launch, or None where the form query answers 0 (or
+    the sources are not laid out as the query assumes): the caller then takes the ordinary path."""
+    cout = weight.shape[0]
+    if norm.weight is None or norm.bias is None or norm.running_mean is None or norm.weight.shape[0] != cout:
+        return None
+    _check_device(x0)
+    for t, c in ((x0, c0), (x1, c1)):
+        if t is not None and (t.shape[-1] != ceil4(c) or t.data_ptr() % 16 or not t.is_contiguous()):
+            return None
+    n, hs, ws_, _ = x0.shape
+    h, w = (hs * 2, ws_ * 2) if ups else (hs, ws_)
+    up = subpixel(ups)
+    if pool and (up or h % 2 or w % 2):
+        return None
+    hq, wq, flags = (h // 2, w // 2, 0) if up else (h, w, int(ups) | 2)          # as _conv_launch
+    if _PRECISION[0] == "bf16" and not bf16_excluded(c0 + c1, cout):
+        flags |= 8
+    form = _query("mnk_conv3x3_evalnorm_form", n, hq, wq, c0, c1, cout, flags, int(up), int(pool))
+    if not form:
+        return None
+    if _FUSED_PENDING:
+        import warnings
+        warnings.warn("dropping the output of %d fused convolution(s) whose norm layer never asked for it (an exception between "
+                      "a convolution and its normalisation layer?)" % len(_FUSED_PENDING))
+        _FUSED_PENDING.clear()
+    wp = _packed_fwd_weight(weight, cout, c0, c1, up)
+    mean, _invstd, scale = _bn_eval_coeffs(x0, norm.weight, norm.running_mean, norm.running_var, norm.eps, cout)
+    z = torch.empty(n, h // 2 if pool else h, w // 2 if pool else w, ceil4(cout), dtype=torch.float32, device=x0.device)
+    ld1 = x1.shape[-1] if x1 is not None else 0
+    head = (x0, _p(x0), x0.shape[-1], c0, _p(x1), ld1, c1, flags, _p(wp), _p(bias), _p(mean), _p(scale), _p(norm.bias), int(relu))
+    if up:
+        _call("mnk_conv3x3_up_fwd_evalnorm", *head, _p(z), z.shape[-1], n, hq, wq, cout)
+    else:
+        _call("mnk_conv3x3_fwd_evalnorm", *head, int(pool), _p(z), z.shape[-1], n, h, w, cout)
+    EVAL_NORM_COUNT[form - 1] += 1
+    _FUSED_PENDING[z.data_ptr()] = (z, norm, bool(relu), bool(pool))
+    return z
+
+
+def conv3x3(x0, c0, weight, bias=None, x1=None, c1=0, ups=False, residual=None, want_stats=False, skip=False, eval_bn=False,
+            follow=None):
     """-> (y, sums): sums = fused BatchNorm statistics [sum, sum of squares] of y when want_stats, else None.
     skip: -> (y, sums, x0 handed through for x0's other consumer), see Conv3x3SkipFn.
     eval_bn: the caller vouches that y's ONLY consumer is the evaluation-mode norm layer it calls next (bn_act): under no_grad a
     split-K launch then leaves its partials to that layer (mnk_bn_eval_split_fwd: reduction + affine + ReLU + pool in one launch)
-    and y is never written."""
+    and y is never written.
+    follow: (norm, relu, pool) of that bn_act call.  Inside eval_norm_fusion(True) an unsplit launch then applies the layer itself
+    and what comes back as `y` is the finished z: the bn_act that follows recognises it and hands it through."""
     if _PRECISION[0] != "fp32":
         if torch.is_grad_enabled():
             raise RuntimeError("a convolution with gradients enabled inside inference_precision(%r): the backward kernels are "
@@ -1071,6 +1156,12 @@ def conv3x3(x0, c0, weight, bias=None, x1=None, c1=0, ups=False, residual=None, 
         t is not None and t.requires_grad for t in (x0, x1, weight, bias, residual))
     eval_defer = bool(eval_bn and not want_stats and residual is None and not torch.is_grad_enabled()
                       and knobs.form("EVAL_SPLIT_FUSED"))
+    pair = eval_defer and follow is not None and not follow[0].training
+    if pair and _FUSE_NORM[0]:
+        # a conv -> evaluation-mode norm pair under no_grad: fused where the scope is on and the library has the form
+        z = _conv_evalnorm(x0, c0, x1, c1, ups, weight, bias, *follow)
+        if z is not None:
+            return (z, None, x0) if skip else (z, None)
     src_bn = (_bn_of(x0), _bn_of(x1)) if track else None     # the norm layers whose outputs the sources are (see _BN_OF)
     # training_precision("bf16"): a call with gradients enabled; no_grad calls are left to inference_precision
     train_bf16 = _TRAIN_PRECISION[0] == "bf16" and torch.is_grad_enabled()
@@ -1079,6 +1170,8 @@ def conv3x3(x0, c0, weight, bias=None, x1=None, c1=0, ups=False, residual=None, 
         y, sums, through = Conv3x3SkipFn.apply(*args)
         return y, (sums if want_stats else None), through
     y, sums = Conv3x3Fn.apply(*args)
+    if pair:
+        _PAIR_PENDING[0] = y.data_ptr()      # bn_act counts the pair: deferred split-K or separate launches (EVAL_NORM_COUNT)
     return (y, (sums if want_stats else None), x0) if skip else (y, (sums if want_stats else None))
 
 
@@ -1314,6 +1407,17 @@ class BNActSkipFn(_Fn):
 def bn_act(y, c, norm, relu=True, pool=False, sums=None, skip=False):
     """`norm` is a sync_batchnorm.SynchronizedBatchNorm3d parameter holder; `sums` = statistics of y that a conv
     epilogue already produced (training mode).  skip: -> (z, y handed through for a residual add), see BNActSkipFn."""
+    if _FUSED_PENDING:
+        # y is the finished z of a fused convolution (conv3x3(follow=...) inside eval_norm_fusion): hand it through
+        done = _FUSED_PENDING.pop(y.data_ptr(), None)
+        if done is not None:
+            if done[0] is not y or done[1] is not norm or done[2:] != (bool(relu), bool(pool)) or skip or y.shape[-1] != ceil4(c):
+                raise RuntimeError("a convolution applied the norm layer its caller announced (conv3x3(follow=...)), and another "
+                                   "bn_act call followed it")
+            return y
+    pair, _PAIR_PENDING[0] = _PAIR_PENDING[0], None
+    if pair is not None and pair == y.data_ptr() and not norm.training and not torch.is_grad_enabled():
+        EVAL_NORM_COUNT[2 if pair in _SPLIT_PENDING else 3] += 1
     fn = BNActSkipFn if skip and knobs.form("RES_SKIP_FUSED") else BNActFn
     _LAST_BN[0] = None
     out = fn.apply(y, norm.weight, norm.bias, norm.running_mean, norm.running_var,

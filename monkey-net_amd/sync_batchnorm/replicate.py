@@ -139,10 +139,11 @@ class DataParallelWithCallback(nn.Module):
                     return out
             if not torch.is_grad_enabled():
                 # the eager fall-backs (MNK_EVAL_GRAPH=0, a signature the runner declines) in the precision the runner would have
-                # captured in: MNK_EVAL_PRECISION, or the enclosing scope (with gradients enabled the variable does not apply)
+                # captured in: MNK_EVAL_PRECISION, or the enclosing scope (with gradients enabled the variable does not apply);
+                # likewise MNK_EVAL_FUSE_NORM
                 from mnk import ops as mops
                 inputs, kwargs = self._scatter(inputs, kwargs, dev)
-                with mops.inference_precision(dropin.eval_precision()):
+                with mops.inference_precision(dropin.eval_precision()), mops.eval_norm_fusion(dropin.eval_fuse_norm()):
                     return self.module(*_to_device(inputs, dev), **_to_device(kwargs, dev))
         inputs, kwargs = self._scatter(inputs, kwargs, dev)
         return self.module(*_to_device(inputs, dev), **_to_device(kwargs, dev))

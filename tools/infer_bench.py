@@ -4,7 +4,12 @@ Default (BASELINE config 5): bair 64x64, batch 512 -- frames/s for eager launche
 --precision-ab: fp32 against the opt-in bf16 inference mode (precision="bf16": the 3x3 convolutions round their operands to
 bf16) at four configurations -- bair batch 512 @ 64 eager, moving-gif batch 64 @ 64, vox batch 8 @ 256, and the reference's
 batch-1 frame loop behind DataParallelWithCallback (mnk.dropin.EvalRunner under MNK_EVAL_PRECISION).  The two forms alternate,
-`--reps` timings each; median and spread (max - min) per form, one JSON line per configuration."""
+`--reps` timings each; median and spread (max - min) per form, one JSON line per configuration.
+--fuse-ab: the default against the opt-in evaluation-mode norm fusion (fuse_norm=True / MNK_EVAL_FUSE_NORM=1: unsplit convolutions
+apply the norm layer, ReLU and pool behind them in their own epilogue) at the same four configurations, in fp32 and in bf16;
+alternating timings as above, plus -- for the batched configurations -- the conv and norm-apply kernel groups of the library's
+event recorder per forward in either form (what the separate norm passes cost) and the count of fused / deferred / separate
+conv -> norm pairs."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "monkey-net_amd"))
@@ -16,7 +21,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--config", default="bair"); ap.add_argument("--batch", type=int, default=512)
 ap.add_argument("--size", type=int, default=64); ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--precision-ab", action="store_true"); ap.add_argument("--reps", type=int, default=5)
-ap.add_argument("--only", default="", help="--precision-ab: comma-separated subset of bair,moving-gif,vox,frame-loop")
+ap.add_argument("--fuse-ab", action="store_true")
+ap.add_argument("--only", default="", help="--precision-ab / --fuse-ab: comma-separated subset of bair,moving-gif,vox,frame-loop")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 
@@ -76,6 +82,64 @@ def frame_loop_ab(config, size, frames, iters):
     return {"workload": "%s frame loop through EvalRunner, batch 1 @ %dx%d, %d frames per loop" % (config, size, size, frames), **res,
             "speedup": round(res["fp32"]["ms"] / res["bf16"]["ms"], 3)}
 
+
+def reconstructor_fuse_ab(config, batch, size, iters, precision):
+    from mnk import _lib, ops
+    gen, disc, kpd = bench.build_models(configs.get(config), dev)
+    src = torch.rand(batch, 3, 1, size, size, device=dev)
+    drv = torch.rand(batch, 3, 1, size, size, device=dev)
+    recs = {f: engine.Reconstructor(kpd, gen, precision=precision, fuse_norm=(f == "fused")) for f in ("default", "fused")}
+    res = alternate({f: (lambda r=r: r(src, drv)) for f, r in recs.items()}, iters, args.reps)
+    a, b = recs["default"](src, drv), recs["fused"](src, drv)
+    res["outputs_equal"] = all(torch.equal(a[k], b[k]) for k in a)
+    for f, r in recs.items():
+        ops.clear_eval_norm_count()
+        r(src, drv)
+        res[f]["pairs_fused_elem_pool_deferred_separate"] = list(ops.EVAL_NORM_COUNT)
+        groups = bench.prof_collect(_lib.lib(), lambda r=r: r(src, drv), 3)
+        res[f]["groups"] = {k: {"launches": round(v["launches_per_step"], 1), "ms": round(v["ms_per_step"], 4)}
+                            for k, v in groups.items() if k in ("conv3x3_igemm", "bn_act_apply", "conv3x3_reduce_pack")}
+        res[f]["all_groups_ms"] = round(sum(v["ms_per_step"] for v in groups.values()), 4)
+    return {"workload": "%s Reconstructor eager, %s, batch %d @ %dx%d" % (config, precision, batch, size, size), **res,
+            "speedup": round(res["default"]["ms"] / res["fused"]["ms"], 3)}
+
+
+def frame_loop_fuse_ab(config, size, frames, iters, precision):
+    """frame_loop_ab with MNK_EVAL_FUSE_NORM alternating"""
+    from sync_batchnorm import DataParallelWithCallback
+    gen, disc, kpd = bench.build_models(configs.get(config), dev)
+    generator, kp_detector = DataParallelWithCallback(gen), DataParallelWithCallback(kpd)
+    generator.eval(), kp_detector.eval()
+    video = torch.rand(1, 3, frames, size, size, device=dev)
+    os.environ["MNK_EVAL_PRECISION"] = precision
+
+    def loop(fuse):
+        os.environ["MNK_EVAL_FUSE_NORM"] = fuse
+        with torch.no_grad():
+            kp_source = kp_detector(video[:, :, :1])
+            for i in range(frames):
+                kp_driving = kp_detector(video[:, :, i:i + 1])
+                generator(source_image=video[:, :, :1], kp_driving=kp_driving, kp_source=kp_source)
+
+    res = alternate({f: (lambda v=v: loop(v)) for f, v in (("default", "0"), ("fused", "1"))}, iters, args.reps)
+    os.environ.pop("MNK_EVAL_FUSE_NORM", None); os.environ.pop("MNK_EVAL_PRECISION", None)
+    for v in (res["default"], res["fused"]):
+        v["ms_per_frame"] = round(v["ms"] / frames, 4)
+    return {"workload": "%s frame loop through EvalRunner, %s, batch 1 @ %dx%d, %d frames per loop" % (config, precision, size, size, frames),
+            **res, "speedup": round(res["default"]["ms"] / res["fused"]["ms"], 3)}
+
+
+if args.fuse_ab:
+    only = set(filter(None, args.only.split(",")))
+    for precision in ("fp32", "bf16"):
+        jobs = [("bair", lambda: reconstructor_fuse_ab("bair", 512, 64, args.iters, precision)),
+                ("moving-gif", lambda: reconstructor_fuse_ab("moving-gif", 64, 64, args.iters, precision)),
+                ("vox", lambda: reconstructor_fuse_ab("vox", 8, 256, max(2, args.iters // 2), precision)),
+                ("frame-loop", lambda: frame_loop_fuse_ab("moving-gif", 64, 16, max(2, args.iters // 2), precision))]
+        for name, job in jobs:
+            if not only or name in only:
+                print(json.dumps(job()), flush=True)
+    sys.exit(0)
 
 if args.precision_ab:
     only = set(filter(None, args.only.split(",")))
