@@ -302,7 +302,8 @@ extern "C" {
 
 int mnk_ncdhw_to_nhwc(const float* src, float* dst, int B, int C, int D, int H, int W, int step, int ld_dst,
                       void* stream) {
-    MNK_REQUIRE(src && dst && B > 0 && C > 0 && D > 0 && H > 0 && W > 0 && step >= 1 && ld_dst >= C);
+    MNK_REQUIRE(src && dst && B > 0 && C > 0 && D > 0 && H > 0 && W > 0 && step >= 1 && ld_dst >= C && H / step > 0 &&
+                W / step > 0);
     hipStream_t s = (hipStream_t)stream;
     long total = (long)B * D * (H / step) * (W / step);
     ProfScope prof(K_LAYOUT, s, (double)total * (C + ld_dst) * 4);

@@ -300,10 +300,25 @@ def dense_motion_forward(ctx, prefix, p, common, source_image, kp_driving, kp_so
     return field.view(b, d, h, w, 3)
 
 
+def nearest_index(in_size, out_size):
+    """The source index of every destination index under F.interpolate(mode='nearest') as the reference
+    runs it, on float32 tensors: floorf(dst * ((float)in / (float)out)) clamped to in - 1 (ATen
+    nearest_neighbor_compute_source_index with a float scale).  On float64 5-D input ATen's pick equals
+    the rational floor(dst * in / out) instead, which differs at a few size pairs such as (26, 22)
+    (tests/test_kernels_geometry_ratios.py lists them): gathering with this index keeps the fp64 oracle on the
+    reference's texels.  Long tensor of out_size entries."""
+    scale = torch.tensor(float(in_size), dtype=torch.float32) / torch.tensor(float(out_size), dtype=torch.float32)
+    src = torch.floor(torch.arange(out_size, dtype=torch.float32) * scale).long()
+    return src.clamp(max=in_size - 1)
+
+
 def resize_field(field, size, mode):
     """generator.py:53-56: field (B,d,ho,wo,3) -> (B,d,h,w,3).  d stays, so 'trilinear' is bilinear
-    (align_corners=False) in h,w and 'nearest' is an index pick."""
+    (align_corners=False) in h,w and 'nearest' is an index pick (nearest_index: the reference's fp32
+    pick for every dtype)."""
     b, d, ho, wo, _ = field.shape
+    if mode == "nearest":
+        return field[:, :, nearest_index(ho, size[0])][:, :, :, nearest_index(wo, size[1])]
     f = field.permute(0, 4, 1, 2, 3)
     f = F.interpolate(f, size=(d,) + tuple(size), mode=mode)
     return f.permute(0, 2, 3, 4, 1)

@@ -10,6 +10,7 @@ import torch.nn.functional as F
 from _util import to_nhwc, from_nhwc, ceil4, relerr, maxerr
 from _guard import be  # noqa: F401  (guard-banded buffers, checked calls)
 from oracle import restate
+from _warp_levels import WARP_TABLES, run_warp_levels
 
 
 @pytest.mark.parametrize("G,S", [(11, 4), (5, 6), (3, 1)])
@@ -362,44 +363,6 @@ def test_concat2_direct(be, ca, cb, halves):
     assert torch.equal(GA2.cpu(), ga)
 
 
-# (C, h, w, the key-point embedding behind the warp, d input wanted); "decoder": the levels of
-# test_all_warps_in_one_launch_equal_the_per_level_launches; "edges": one texel, channel slices (C = 300), a level without d input
-WARP_TABLES = {
-    "decoder": [(8, 4, 4, True, True), (5, 8, 8, False, True), (4, 16, 16, True, True), (3, 32, 32, False, True)],
-    "edges": [(7, 1, 1, True, True), (300, 4, 4, False, True), (5, 8, 8, True, False)],
-}
-_WARP_REFS = {}
-
-
-def _warp_case(table, mode, with_emb):
-    """inputs of the levels (test_deform's kinds: uniform images, identity + 0.4 * noise field) and fp64 autograd through
-    restate.deform_input and the resized embedding (generator.py:60-78), cached for the parameters that share it"""
-    key = (table, mode, with_emb)
-    if key not in _WARP_REFS:
-        g = torch.Generator().manual_seed(16)
-        n, hf, wf, he, emb_ch = 2, 16, 16, 8, 6
-        name = "nearest" if mode == 0 else "trilinear"
-        field = restate.make_coordinate_grid(hf, wf).view(1, hf, wf, 2).repeat(n, 1, 1, 1) + 0.4 * torch.randn(n, hf, wf, 2, generator=g)
-        emb = torch.randn(n, emb_ch, he, he, generator=g)
-        levels = [(c, h, w, emb_ch if (k and with_emb) else 0, di) for c, h, w, k, di in WARP_TABLES[table]]
-        inps = [torch.rand(n, c, h, w, generator=g) for c, h, w, _, _ in levels]
-        douts = [torch.randn(n, c + ke, h, w, generator=g) for c, h, w, ke, _ in levels]
-        f64 = torch.cat([field, torch.zeros(n, hf, wf, 1)], -1).view(n, 1, hf, wf, 3).double().requires_grad_(True)
-        e64 = emb.double().requires_grad_(True)
-        x64 = [x.double().requires_grad_(True) for x in inps]
-        outs = []
-        for x, (c, h, w, ke, _) in zip(x64, levels):
-            o = restate.deform_input(x.unsqueeze(2), f64, name)[:, :, 0]
-            if ke:
-                o = torch.cat([o, F.interpolate(e64.unsqueeze(2), size=(1, h, w), mode=name)[:, :, 0]], 1)
-            outs.append(o)
-        torch.autograd.backward(outs, [d.double() for d in douts])
-        _WARP_REFS[key] = dict(n=n, hf=hf, wf=wf, he=he, emb_ch=emb_ch, levels=levels, field=field, emb=emb, inps=inps, douts=douts,
-                               outs=[o.detach() for o in outs], dinps=[x.grad for x in x64], dfield=f64.grad[:, 0, :, :, :2],
-                               demb=e64.grad)
-    return _WARP_REFS[key]
-
-
 @pytest.mark.parametrize("want", ["all", "no-emb", "no-dfield", "no-demb"])
 @pytest.mark.parametrize("mode", [0, 1])
 @pytest.mark.parametrize("table", list(WARP_TABLES))
@@ -408,46 +371,6 @@ def test_warp_levels_direct(be, table, mode, want):
     autograd (tolerances of test_deform): every channel of every out_l written (pad channels 0), d input written with pad
     channels 0 (or absent), d field summed over the levels, d embedding over the levels that carry it; emb / dfield / demb
     NULL in turn.  The tables' pointers are host data the guarded call cannot see: inputs are compared with copies, the
-    guards checked after the launches."""
-    from test_multiframe_kernels import WARP_LEVEL
-    import numpy as np
-    r = _warp_case(table, mode, want != "no-emb")
-    n, hf, wf, he, emb_ch, levels = r["n"], r["hf"], r["wf"], r["he"], r["emb_ch"], r["levels"]
-    with_emb = want != "no-emb"
-    lde = ceil4(emb_ch) if with_emb else 0
-    FL = be.t(r["field"])
-    EMB = be.t(to_nhwc(r["emb"])) if with_emb else None
-    XS = [be.t(to_nhwc(x)) for x in r["inps"]]
-    DOS = [be.t(to_nhwc(d)) for d in r["douts"]]
-    OUTS = [be.empty(n, h, w, ceil4(c + ke)) for c, h, w, ke, _ in levels]
-    DIS = [be.empty(n, h, w, ceil4(c)) if di else None for c, h, w, _, di in levels]
-    lv = np.zeros(len(levels), dtype=WARP_LEVEL)
-    for i, (c, h, w, ke, _) in enumerate(levels):
-        lv[i] = (XS[i].data_ptr(), OUTS[i].data_ptr(), DOS[i].data_ptr(), DIS[i].data_ptr() if DIS[i] is not None else 0,
-                 XS[i].shape[-1], c, h, w, OUTS[i].shape[-1], ke, c, 0)
-    keep = [t.clone() for t in XS + DOS]
-    hw_e = he if with_emb else 0
-    be.call("mnk_warp_levels_fwd", lv.ctypes.data, len(levels), FL, hf, wf, mode, EMB, lde, hw_e, hw_e, n)
-    nws = be.query("mnk_warp_levels_bwd_workspace_floats", lv.ctypes.data, len(levels), n)
-    assert nws > 0
-    DF = be.empty(n, hf, wf, 2) if want != "no-dfield" else None
-    DE = be.empty(n, he, he, lde) if with_emb and want != "no-demb" else None
-    be.call("mnk_warp_levels_bwd", lv.ctypes.data, len(levels), FL, hf, wf, mode, DF, DE, lde, hw_e, hw_e, n, be.empty(nws), nws)
-    be.sync()
-    be.check_all("after the launches")
-    for t, k in zip(XS + DOS, keep):
-        assert torch.equal(t.view(torch.int32), k.view(torch.int32)), "an input named in the level table was written"
-    for (c, h, w, ke, di), O, DI, ro, rdi in zip(levels, OUTS, DIS, r["outs"], r["dinps"]):
-        o = O.cpu()
-        assert maxerr(from_nhwc(o, c + ke), ro) < 1e-5, (c, h, w)
-        assert torch.all(o[..., c + ke:] == 0), (c, h, w)
-        if di:
-            d = DI.cpu()
-            assert torch.all(d[..., c:] == 0), (c, h, w)
-            assert relerr(from_nhwc(d, c), rdi) < 1e-5, (c, h, w)
-    if DF is not None:
-        assert relerr(DF.cpu(), r["dfield"]) < 1e-5
-    if DE is not None:
-        de = DE.cpu()
-        assert torch.all(de[..., emb_ch:] == 0)
-        assert relerr(from_nhwc(de, emb_ch), r["demb"]) < 1e-5
+    guards checked after the launches.  (The body is _warp_levels.run_warp_levels, shared with the tables off the
+    power-of-two grid of test_kernels_geometry_ratios.py.)"""
+    run_warp_levels(be, table, mode, want)
