@@ -291,6 +291,37 @@ int mnk_conv3x3_fwd_evalnorm(const float* x0, int ld0, int C0, const float* x1, 
 int mnk_conv3x3_up_fwd_evalnorm(const float* x0, int ld0, int C0, const float* x1, int ld1, int C1, int flags, const float* wp_up,
                                 const float* bias, const float* mean, const float* scale, const float* beta, int relu, float* z,
                                 int ld_z, int N, int H, int W, int Cout, void* stream);
+/* ---- weight-streaming ("skinny") forward launches for batch-1 evaluation (opt-in) ----------------------------------------------
+ * The reference's evaluation loops call the networks one frame at a time; at the deep hourglass levels a DownBlock3D / UpBlock3D
+ * convolution (modules/util.py:79-88,98-108) then has 1 ... 16 output rows (N * H * W) against up to 38 MB of weights: a GEMV
+ * with a few columns, whose time is the weight stream.  This form reads every weight once per block, 16 bytes per load straight
+ * into registers, over a grid of (32-channel tiles of Cout) x (K splits) so that every CU streams, and multiplies in fp32 fmaf
+ * chains of a fixed order (no atomics, no hand-over between blocks).  It writes ONLY split partials -- `ws` =
+ * [split][N * H * W][round_up(Cout, 4)], bias not added -- which mnk_bn_eval_split_fwd(ws, splits, ldw, phases = 1, ...) sums in
+ * order and finishes (bias, evaluation-mode norm affine, ReLU, 2x2 pool: modules/util.py:81-87,100-107).
+ *   pack: mnk_conv3x3_skinny_pack takes the reference's (Cout, C0 + C1, 1, 3, 3) parameter (modules/util.py:79,98) as it is.
+ *         Layout [Cout tile of 32][k pair][channel quad][k parity][4] with k = tap * (C0 + C1) + ci, zero-filled to a multiple of 64
+ *         k and 32 channels: a block's weight stream is one contiguous run.  `bf16` = 1 stores round-to-nearest-even bf16 elements
+ *         (what MNK_CONV_BF16 launches read: the values the loaders of the one-pass kernels would round to, at half the bytes);
+ *         mnk_conv3x3_skinny_packed_floats counts in floats either way (a bf16 pack is half as long).
+ *   flags: MNK_CONV_UPSAMPLED (the sources are (H / 2, W / 2), read at (y >> 1, x >> 1) with the plain nine taps, modules/util.py:84
+ *          -- not the sub-pixel packs, which hold 16/9 of the weight bytes) | MNK_CONV_CLEAN_PADS (accepted; pad channels are
+ *          never read) | MNK_CONV_DEFER_SPLITK (accepted: what this entry always does) | MNK_CONV_BF16 (both operands rounded to
+ *          nearest-even bf16 -- the activations in the loader, the weights in a bf16 pack -- exact products, fp32 accumulation).
+ *   mnk_conv3x3_skinny_form: 1 when a launch at this shape takes the form under the current tuning -- N * H * W <= "skinny_rows"
+ *          (mnk_set_tuning; at most 64), H and W even for an up-sampled or pooled (`pool`: the norm layer behind pools) layer,
+ *          no other flag, and -- measured -- an up-sampled layer only with 9 (C0 + C1) Cout >= "skinny_up_min_weights" (8 Mi) or,
+ *          under MNK_CONV_BF16, with at most 4 rows (shorter weight streams are level with the sub-pixel launch) -- else 0: mnk_conv3x3_skinny_fwd then returns MNK_EINVAL, launches nothing and writes nothing.
+ *   mnk_conv3x3_skinny_splits / _workspace_floats: the K splits of the launch (a rule from Cout, K and the CU count --
+ *          "skinny_blocks" blocks, no split shorter than "skinny_min_k" -- overridden by "force_splits") and splits * N * H * W *
+ *          round_up(Cout, 4).  mnk_last_plan after a launch: {N * H * W, Cout, K / 64, 9, 1, rows per block, 32, splits}. */
+size_t mnk_conv3x3_skinny_packed_floats(int Cout, int C0, int C1, int bf16);
+int mnk_conv3x3_skinny_pack(const float* w, float* wp, int Cout, int C0, int C1, int bf16, void* stream);
+int mnk_conv3x3_skinny_form(int N, int H, int W, int C0, int C1, int Cout, int flags, int pool);
+int mnk_conv3x3_skinny_splits(int N, int H, int W, int C0, int C1, int Cout);
+size_t mnk_conv3x3_skinny_workspace_floats(int N, int H, int W, int C0, int C1, int Cout);
+int mnk_conv3x3_skinny_fwd(const float* x0, int ld0, int C0, const float* x1, int ld1, int C1, int flags, const float* wp, int N,
+                           int H, int W, int Cout, float* ws, size_t ws_floats, void* stream);
 /* dw[co][c_start+ci][ky][kx] = sum_pixels dy[p][co] * x[p+tap][ci]; x is one source (C channels)
  * `flags`: MNK_CONV_UPSAMPLED | MNK_CONV_CLEAN_PADS | MNK_WGRAD_DEFER | MNK_WGRAD_BF16 (below) */
 size_t mnk_conv3x3_wgrad_workspace_floats(int N, int H, int W, int C, int Cout);

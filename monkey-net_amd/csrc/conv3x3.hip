@@ -1648,8 +1648,12 @@ static const PlanRow g_tuned_rows_bf16x3[] = {
 #include "plan_table_bf16x3.h"
     {0, 0, 0, 0, 0, 0, 0, 0}};
 static int g_plan_table = tuning_knob("plan_table", &g_plan_table, 1), g_force_bm = tuning_knob("force_bm", &g_force_bm, 0),
-           g_force_bn = tuning_knob("force_bn", &g_force_bn, 0), g_force_splits = tuning_knob("force_splits", &g_force_splits, 0);
-static long g_last_plan[8];
+           g_force_bn = tuning_knob("force_bn", &g_force_bn, 0);
+}  // namespace
+// shared with conv_skinny.hip (declared in conv_common.h): the forced split count and the plan mnk_last_plan reports
+int mnk::g_force_splits = tuning_knob("force_splits", &mnk::g_force_splits, 0);
+long mnk::g_last_plan[8];
+namespace {
 
 // block tiles the GEMM kernels are instantiated for (conv2d_fwd_impl's dispatch)
 static bool plan_tile_ok(int bm, int bn, int Cout, int phases) {

@@ -10,6 +10,10 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // each, defined in conv3x3.hip: mnk_set_tuning writes the first slot registered under a name and stops
 namespace mnk {
 extern __attribute__((visibility("hidden"))) int g_xcd_remap, g_fast_loader;
+// "force_splits" and the plan mnk_last_plan reports ({M, Cout, chunks, taps, phases, bm, bn, splits}): conv3x3.hip's, also read and
+// written by the weight-streaming form (conv_skinny.hip)
+extern __attribute__((visibility("hidden"))) int g_force_splits;
+extern __attribute__((visibility("hidden"))) long g_last_plan[8];
 }
 
 namespace {

@@ -465,7 +465,8 @@ class EvalRunner:
     calls).  Re-captured when a parameter, a buffer or the optimiser epoch changed (load_state_dict between two videos).
     The forward is captured inside ops.inference_precision(eval_precision()) -- an enclosing bf16 scope, else MNK_EVAL_PRECISION;
     the precision is part of the program key, so a changed scope or variable captures a program of its own instead of replaying
-    the other form.  The same holds for ops.eval_norm_fusion(eval_fuse_norm()): an enclosing scope, else MNK_EVAL_FUSE_NORM."""
+    the other form.  The same holds for ops.eval_norm_fusion(eval_fuse_norm()): an enclosing scope, else MNK_EVAL_FUSE_NORM, and for
+    ops.eval_skinny_conv(eval_skinny()): an enclosing scope, else MNK_EVAL_SKINNY."""
 
     MAX_PROGRAMS = 8
 
@@ -506,14 +507,14 @@ class EvalRunner:
         key = self._flatten((inputs, kwargs), flat)
         if not flat or any(t.dtype != torch.float32 for _, t in flat):
             return NotImplemented
-        precision, fuse = eval_precision(), eval_fuse_norm()
-        key = (precision, fuse, key)
+        precision, fuse, skinny = eval_precision(), eval_fuse_norm(), eval_skinny()
+        key = (precision, fuse, skinny, key)
         fp = self._fingerprint(module)
         prog = self.programs.get(key)
         if prog is None or prog["fp"] != fp:
             if len(self.programs) >= self.MAX_PROGRAMS:
                 self.programs.clear()
-            prog = self.programs[key] = self._capture(module, inputs, kwargs, flat, device, fp, precision, fuse)
+            prog = self.programs[key] = self._capture(module, inputs, kwargs, flat, device, fp, precision, fuse, skinny)
         dsts, srcs = [], []
         for i, ((path, t), s) in enumerate(zip(flat, prog["static"])):
             if t.device.type == "cpu" and not t.is_pinned():
@@ -551,14 +552,14 @@ class EvalRunner:
         ring["buf"][k].copy_(t)
         return ring["buf"][k], ring["ev"][k]
 
-    def _capture(self, module, inputs, kwargs, flat, device, fp, precision="fp32", fuse=False):
+    def _capture(self, module, inputs, kwargs, flat, device, fp, precision="fp32", fuse=False, skinny=False):
         static = [t.to(device).clone() for _, t in flat]
         leaves = {path: s for (path, _), s in zip(flat, static)}
         s_in, s_kw = self._rebuild((inputs, kwargs), leaves)
         cap = torch.cuda.Stream()
         cap.wait_stream(torch.cuda.current_stream())
         # (the caches are keyed by stream: fill them on the stream the capture runs on)
-        with torch.cuda.stream(cap), mops.inference_precision(precision), mops.eval_norm_fusion(fuse):
+        with torch.cuda.stream(cap), mops.inference_precision(precision), mops.eval_norm_fusion(fuse), mops.eval_skinny_conv(skinny):
             for _ in range(2):
                 module(*s_in, **s_kw)
         torch.cuda.current_stream().wait_stream(cap)
@@ -566,7 +567,8 @@ class EvalRunner:
         graph = torch.cuda.CUDAGraph()
         mops.FROZEN_CAPTURE[0] = True
         try:
-            with torch.cuda.graph(graph, stream=cap), mops.inference_precision(precision), mops.eval_norm_fusion(fuse):
+            with torch.cuda.graph(graph, stream=cap), mops.inference_precision(precision), mops.eval_norm_fusion(fuse), \
+                    mops.eval_skinny_conv(skinny):
                 out = module(*s_in, **s_kw)
         finally:
             mops.FROZEN_CAPTURE[0] = False
@@ -607,6 +609,12 @@ def eval_fuse_norm():
     """whether an evaluation-mode forward behind DataParallelWithCallback runs inside ops.eval_norm_fusion: an enclosing scope that
     is on, else MNK_EVAL_FUSE_NORM.  Like eval_precision it is part of the captured program's key and the eager fall-backs use it."""
     return bool(mops.current_norm_fusion() or knobs.on("MNK_EVAL_FUSE_NORM"))
+
+
+def eval_skinny():
+    """whether an evaluation-mode forward behind DataParallelWithCallback runs inside ops.eval_skinny_conv: an enclosing scope that
+    is on, else MNK_EVAL_SKINNY.  Part of the captured program's key, and the eager fall-backs use it, like eval_fuse_norm."""
+    return bool(mops.current_skinny_conv() or knobs.on("MNK_EVAL_SKINNY"))
 
 
 def eval_runner_for(wrapper):

@@ -566,12 +566,15 @@ class Reconstructor:
     operands to bf16 ("bf16 inference").  A captured graph keeps the precision it was built with.
     fuse_norm: the forward runs inside ops.eval_norm_fusion(fuse_norm): unsplit convolutions apply the evaluation-mode norm
     layer, ReLU and pool behind them in their own epilogue; the outputs are equal to the default's.  A
-    captured graph keeps the form it was built with."""
+    captured graph keeps the form it was built with.
+    skinny: the forward runs inside ops.eval_skinny_conv(skinny): conv -> norm pairs with few output rows (batch 1: the deep
+    hourglass levels) run as weight-streaming launches; a batched call has no such layer and is unchanged."""
 
-    def __init__(self, kp_detector, generator, use_graph=False, precision="fp32", fuse_norm=False):
+    def __init__(self, kp_detector, generator, use_graph=False, precision="fp32", fuse_norm=False, skinny=False):
         self.kp_detector, self.generator = kp_detector.eval(), generator.eval()
         self.precision = mops.check_precision(precision)
         self.fuse_norm = bool(fuse_norm)
+        self.skinny = bool(skinny)
         self.use_graph = bool(use_graph)
         self._graph = None
         self._static_in = None
@@ -579,7 +582,7 @@ class Reconstructor:
 
     @torch.no_grad()
     def _forward(self, source, driving):
-        with mops.inference_precision(self.precision), mops.eval_norm_fusion(self.fuse_norm):
+        with mops.inference_precision(self.precision), mops.eval_norm_fusion(self.fuse_norm), mops.eval_skinny_conv(self.skinny):
             kp_source = self.kp_detector(source)
             kp_driving = self.kp_detector(driving)
             out = self.generator(source, kp_driving=kp_driving, kp_source=kp_source)
@@ -653,17 +656,20 @@ class Transfer:
     key points as they are: the appearance encoder runs once per source instead of once per frame, and its skip tensors
     exist once (B instead of B*d rows); False repeats the source d times along the batch axis.
     precision: "fp32" or "bf16", the ops.inference_precision scope the call runs in (see Reconstructor); fuse_norm: the
-    ops.eval_norm_fusion scope it runs in (see Reconstructor)."""
+    ops.eval_norm_fusion scope it runs in (see Reconstructor); skinny: the ops.eval_skinny_conv scope (see Reconstructor)."""
 
-    def __init__(self, kp_detector, generator, normalization_params, shared_source=False, precision="fp32", fuse_norm=False):
+    def __init__(self, kp_detector, generator, normalization_params, shared_source=False, precision="fp32", fuse_norm=False,
+                 skinny=False):
         self.kp_detector, self.generator = kp_detector.eval(), generator.eval()
         self.precision = mops.check_precision(precision)
         self.fuse_norm = bool(fuse_norm)
+        self.skinny = bool(skinny)
         self.params = dict(normalization_params)
         self.shared_source = bool(shared_source)
 
     def __call__(self, source_image, driving_video):
-        with torch.no_grad(), mops.inference_precision(self.precision), mops.eval_norm_fusion(self.fuse_norm):
+        with torch.no_grad(), mops.inference_precision(self.precision), mops.eval_norm_fusion(self.fuse_norm), \
+                mops.eval_skinny_conv(self.skinny):
             return self._run(source_image, driving_video)
 
     def _run(self, source_image, driving_video):

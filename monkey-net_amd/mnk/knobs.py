@@ -43,6 +43,12 @@ KNOBS = {
                                 "fall-backs) runs inside mnk.ops.eval_norm_fusion: unsplit 3x3 convolutions apply the norm layer, ReLU "
                                 "and pool behind them in their own epilogue; same outputs (INTEGRATION.md 2e).  Part of the captured "
                                 "program's key: changing the variable re-captures.  An enclosing scope that is on takes precedence"),
+    "MNK_EVAL_SKINNY": ("0", "1: the evaluation-mode forward that mnk.dropin.EvalRunner captures (and the wrapper's eager fall-backs) "
+                             "runs inside mnk.ops.eval_skinny_conv: 3x3 conv -> norm pairs with at most `skinny_rows` output rows (the "
+                             "deep hourglass levels of a batch-1 frame; skinny_rows = 16) run as weight-streaming launches: the moving-gif "
+                             "frame 0.854 -> 0.773 ms in fp32, 0.820 -> 0.703 in bf16 (INTEGRATION.md 2f, "
+                             "profiles/eval_skinny.txt).  Part of the captured program's key: changing the variable re-captures.  "
+                             "An enclosing scope that is on takes precedence"),
     "MNK_TRAIN_PRECISION": ("fp32", "the training iteration that mnk.dropin.TrainPairRunner serves behind the reference's own train.py: "
                                     "fp32, or bf16 = the 3x3 convolutions run forward, data gradient and weight gradient on "
                                     "bf16-rounded operands with fp32 accumulation (mnk.ops.training_precision; INTEGRATION.md 2d).  Part "

@@ -1136,6 +1136,96 @@ def _conv_evalnorm(x0, c0, x1, c1, ups, weight, bias, norm, relu, pool):
     return z
 
 
+# ---- opt-in weight-streaming ("skinny") convolutions for batch-1 evaluation ---------------------------------------------------
+# Inside `eval_skinny_conv(True)` a 3x3 or up-sampled 3x3 convolution launched under torch.no_grad() for a caller that vouches for
+# its evaluation-mode norm layer (conv3x3(eval_bn=True, follow=...)) and whose output has few rows (mnk_conv3x3_skinny_form: at
+# most "skinny_rows") runs as mnk_conv3x3_skinny_fwd on a pack of its own (plain nine taps, bf16 elements under
+# inference_precision("bf16")) and leaves split partials to the norm layer through the deferred split-K hand-over
+# (_SPLIT_PENDING -> mnk_bn_eval_split_fwd).  With gradients enabled, in training, or with the scope off nothing changes.
+_SKINNY = [False]
+EVAL_SKINNY_COUNT = [0]                   # layers that took the form since clear_eval_skinny_count()
+_SKINNY_PACK_CACHE = {}
+
+
+class eval_skinny_conv:
+    """Context manager: `with eval_skinny_conv(True):` (see above).  One value per process, like eval_norm_fusion; the previous
+    value is restored on exit, also after an exception."""
+
+    def __init__(self, on=True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.previous = _SKINNY[0]
+        _SKINNY[0] = self.on
+        return self
+
+    def __exit__(self, *exc):
+        _SKINNY[0] = self.previous
+        return False
+
+
+def current_skinny_conv():
+    return _SKINNY[0]
+
+
+def clear_eval_skinny_count():
+    EVAL_SKINNY_COUNT[0] = 0
+
+
+def _packed_skinny_weight(weight, cout, c0, c1, bf16):
+    """The skinny pack of a conv weight (mnk_conv3x3_skinny_pack; bf16: half the bytes), cached like _packed_fwd_weight's -- per
+    parameter version, storage, optimiser epoch AND precision -- and, like it, re-made inside a capture that is not FROZEN_CAPTURE."""
+    n = _query("mnk_conv3x3_skinny_packed_floats", cout, c0, c1, int(bf16))
+    if weight.is_cuda and torch.cuda.is_current_stream_capturing() and not FROZEN_CAPTURE[0]:
+        wp = torch.empty(n, dtype=torch.float32, device=weight.device)
+        _call("mnk_conv3x3_skinny_pack", weight, _p(weight), _p(wp), cout, c0, c1, int(bf16))
+        return wp
+    key = (id(weight), weight.device, bool(bf16))
+    ver = (weight._version, _PACK_EPOCH[0], weight.data_ptr())
+    hit = _SKINNY_PACK_CACHE.get(key)
+    if hit is not None and hit[0] == ver and hit[1] == (cout, c0, c1) and hit[3]() is weight:
+        return hit[2]
+    wp = torch.empty(n, dtype=torch.float32, device=weight.device)
+    _call("mnk_conv3x3_skinny_pack", weight, _p(weight), _p(wp), cout, c0, c1, int(bf16))
+    if hit is None:
+        weakref.finalize(weight, _SKINNY_PACK_CACHE.pop, key, None)
+    _SKINNY_PACK_CACHE[key] = (ver, (cout, c0, c1), wp, weakref.ref(weight))
+    return wp
+
+
+def _conv_skinny(x0, c0, x1, c1, ups, weight, bias, norm, relu, pool):
+    """conv3x3's weight-streaming form: -> y, a handle that is never written, whose partials wait in _SPLIT_PENDING for the bn_act
+    the caller runs next; or None where the form query answers 0: the caller then takes the ordinary path."""
+    cout = weight.shape[0]
+    _check_device(x0)
+    for t in (x0, x1):
+        if t is not None and not t.is_contiguous():
+            return None
+    n, hs, ws_, _ = x0.shape
+    h, w = (hs * 2, ws_ * 2) if ups else (hs, ws_)
+    if h % 2 or w % 2:                       # the hand-over's condition (BNActFn.forward)
+        return None
+    bf16 = _PRECISION[0] == "bf16" and not bf16_excluded(c0 + c1, cout)
+    flags = int(bool(ups)) | 2 | (8 if bf16 else 0)
+    if not _query("mnk_conv3x3_skinny_form", n, h, w, c0, c1, cout, flags, int(bool(pool))):
+        return None
+    if _SPLIT_PENDING:
+        import warnings
+        warnings.warn("dropping the deferred split-K partial sums of %d convolution(s) whose BatchNorm never ran (an "
+                      "exception between a convolution and its normalisation layer?)" % len(_SPLIT_PENDING))
+        _SPLIT_PENDING.clear()
+    wp = _packed_skinny_weight(weight, cout, c0, c1, bf16)
+    size = (n, h, w, c0, c1, cout)
+    nws = _query("mnk_conv3x3_skinny_workspace_floats", *size)
+    ws = SCRATCH.get("ws", nws, x0)
+    y = torch.empty(n, h, w, ceil4(cout), dtype=torch.float32, device=x0.device)
+    _call("mnk_conv3x3_skinny_fwd", x0, _p(x0), x0.shape[-1], c0, _p(x1), x1.shape[-1] if x1 is not None else 0, c1, flags, _p(wp),
+          n, h, w, cout, _p(ws), nws)
+    _SPLIT_PENDING[y.data_ptr()] = _SplitPending(ws, _query("mnk_conv3x3_skinny_splits", *size), 1, bias)
+    EVAL_SKINNY_COUNT[0] += 1
+    return y
+
+
 def conv3x3(x0, c0, weight, bias=None, x1=None, c1=0, ups=False, residual=None, want_stats=False, skip=False, eval_bn=False,
             follow=None):
     """-> (y, sums): sums = fused BatchNorm statistics [sum, sum of squares] of y when want_stats, else None.
@@ -1157,6 +1247,12 @@ def conv3x3(x0, c0, weight, bias=None, x1=None, c1=0, ups=False, residual=None, 
     eval_defer = bool(eval_bn and not want_stats and residual is None and not torch.is_grad_enabled()
                       and knobs.form("EVAL_SPLIT_FUSED"))
     pair = eval_defer and follow is not None and not follow[0].training
+    if pair and _SKINNY[0]:
+        # few output rows: the weight-streaming launch; its partials go to the norm layer like a deferred split-K launch's
+        y = _conv_skinny(x0, c0, x1, c1, ups, weight, bias, *follow)
+        if y is not None:
+            _PAIR_PENDING[0] = y.data_ptr()
+            return (y, None, x0) if skip else (y, None)
     if pair and _FUSE_NORM[0]:
         # a conv -> evaluation-mode norm pair under no_grad: fused where the scope is on and the library has the form
         z = _conv_evalnorm(x0, c0, x1, c1, ups, weight, bias, *follow)

@@ -143,7 +143,8 @@ class DataParallelWithCallback(nn.Module):
                 # likewise MNK_EVAL_FUSE_NORM
                 from mnk import ops as mops
                 inputs, kwargs = self._scatter(inputs, kwargs, dev)
-                with mops.inference_precision(dropin.eval_precision()), mops.eval_norm_fusion(dropin.eval_fuse_norm()):
+                with mops.inference_precision(dropin.eval_precision()), mops.eval_norm_fusion(dropin.eval_fuse_norm()), \
+                        mops.eval_skinny_conv(dropin.eval_skinny()):
                     return self.module(*_to_device(inputs, dev), **_to_device(kwargs, dev))
         inputs, kwargs = self._scatter(inputs, kwargs, dev)
         return self.module(*_to_device(inputs, dev), **_to_device(kwargs, dev))

@@ -9,7 +9,11 @@ batch-1 frame loop behind DataParallelWithCallback (mnk.dropin.EvalRunner under 
 apply the norm layer, ReLU and pool behind them in their own epilogue) at the same four configurations, in fp32 and in bf16;
 alternating timings as above, plus -- for the batched configurations -- the conv and norm-apply kernel groups of the library's
 event recorder per forward in either form (what the separate norm passes cost) and the count of fused / deferred / separate
-conv -> norm pairs."""
+conv -> norm pairs.
+--skinny-ab: the default against the opt-in weight-streaming convolutions (skinny=True / MNK_EVAL_SKINNY=1: conv -> norm pairs
+with at most `skinny_rows` output rows) -- the batch-1 frame loop through EvalRunner (moving-gif, taichi @ 64, vox @ 256), where
+the form applies, and the batched configurations, where no layer is under the threshold; fp32 and bf16, alternating timings as
+above, the count of layers that took the form, and the largest difference of the outputs."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "monkey-net_amd"))
@@ -22,7 +26,8 @@ ap.add_argument("--config", default="bair"); ap.add_argument("--batch", type=int
 ap.add_argument("--size", type=int, default=64); ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--precision-ab", action="store_true"); ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--fuse-ab", action="store_true")
-ap.add_argument("--only", default="", help="--precision-ab / --fuse-ab: comma-separated subset of bair,moving-gif,vox,frame-loop")
+ap.add_argument("--skinny-ab", action="store_true")
+ap.add_argument("--only", default="", help="--precision-ab / --fuse-ab / --skinny-ab: comma-separated subset of bair,moving-gif,vox,frame-loop")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 
@@ -128,6 +133,65 @@ def frame_loop_fuse_ab(config, size, frames, iters, precision):
     return {"workload": "%s frame loop through EvalRunner, %s, batch 1 @ %dx%d, %d frames per loop" % (config, precision, size, size, frames),
             **res, "speedup": round(res["default"]["ms"] / res["fused"]["ms"], 3)}
 
+
+def reconstructor_skinny_ab(config, batch, size, iters, precision):
+    from mnk import ops
+    gen, disc, kpd = bench.build_models(configs.get(config), dev)
+    src = torch.rand(batch, 3, 1, size, size, device=dev)
+    drv = torch.rand(batch, 3, 1, size, size, device=dev)
+    recs = {f: engine.Reconstructor(kpd, gen, precision=precision, skinny=(f == "skinny")) for f in ("default", "skinny")}
+    res = alternate({f: (lambda r=r: r(src, drv)) for f, r in recs.items()}, iters, args.reps)
+    a, b = recs["default"](src, drv), recs["skinny"](src, drv)
+    res["max_abs_output_difference"] = max(float((a[k] - b[k]).abs().max()) for k in a)
+    ops.clear_eval_skinny_count()
+    recs["skinny"](src, drv)
+    res["skinny_layers"] = ops.EVAL_SKINNY_COUNT[0]
+    return {"workload": "%s Reconstructor eager, %s, batch %d @ %dx%d" % (config, precision, batch, size, size), **res,
+            "speedup": round(res["default"]["ms"] / res["skinny"]["ms"], 3)}
+
+
+def frame_loop_skinny_ab(config, size, frames, iters, precision):
+    """frame_loop_ab with MNK_EVAL_SKINNY alternating"""
+    from sync_batchnorm import DataParallelWithCallback
+    from mnk import ops
+    gen, disc, kpd = bench.build_models(configs.get(config), dev)
+    generator, kp_detector = DataParallelWithCallback(gen), DataParallelWithCallback(kpd)
+    generator.eval(), kp_detector.eval()
+    video = torch.rand(1, 3, frames, size, size, device=dev)
+    os.environ["MNK_EVAL_PRECISION"] = precision
+    last = {}
+
+    def loop(value):
+        os.environ["MNK_EVAL_SKINNY"] = value
+        with torch.no_grad():
+            kp_source = kp_detector(video[:, :, :1])
+            for i in range(frames):
+                kp_driving = kp_detector(video[:, :, i:i + 1])
+                last[value] = generator(source_image=video[:, :, :1], kp_driving=kp_driving, kp_source=kp_source)["video_prediction"]
+
+    ops.clear_eval_skinny_count()
+    res = alternate({f: (lambda v=v: loop(v)) for f, v in (("default", "0"), ("skinny", "1"))}, iters, args.reps)
+    res["skinny_layers_captured"] = ops.EVAL_SKINNY_COUNT[0]      # counted while the programs were captured (warm-up + capture passes)
+    res["max_abs_prediction_difference"] = float((last["0"] - last["1"]).abs().max())
+    os.environ.pop("MNK_EVAL_SKINNY", None); os.environ.pop("MNK_EVAL_PRECISION", None)
+    for v in (res["default"], res["skinny"]):
+        v["ms_per_frame"] = round(v["ms"] / frames, 4)
+    return {"workload": "%s frame loop through EvalRunner, %s, batch 1 @ %dx%d, %d frames per loop" % (config, precision, size, size, frames),
+            **res, "speedup": round(res["default"]["ms"] / res["skinny"]["ms"], 3)}
+
+
+if args.skinny_ab:
+    only = set(filter(None, args.only.split(",")))
+    for precision in ("fp32", "bf16"):
+        jobs = [("frame-loop", lambda: frame_loop_skinny_ab("moving-gif", 64, 16, max(2, args.iters // 2), precision)),
+                ("frame-loop-taichi", lambda: frame_loop_skinny_ab("taichi", 64, 16, max(2, args.iters // 2), precision)),
+                ("frame-loop-vox", lambda: frame_loop_skinny_ab("vox", 256, 8, max(2, args.iters // 2), precision)),
+                ("bair", lambda: reconstructor_skinny_ab("bair", 512, 64, args.iters, precision)),
+                ("moving-gif", lambda: reconstructor_skinny_ab("moving-gif", 64, 64, args.iters, precision))]
+        for name, job in jobs:
+            if not only or name in only:
+                print(json.dumps(job()), flush=True)
+    sys.exit(0)
 
 if args.fuse_ab:
     only = set(filter(None, args.only.split(",")))
