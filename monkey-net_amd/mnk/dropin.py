@@ -463,10 +463,9 @@ class EvalRunner:
     mnk.engine.Reconstructor re-packs inside the graph: right for a batch of 512, most of the launches at batch 1) -- and replayed
     per call: inputs are copied into static buffers, outputs are returned as fresh tensors (the loop keeps `kp_source` across
     calls).  Re-captured when a parameter, a buffer or the optimiser epoch changed (load_state_dict between two videos).
-    The forward is captured inside ops.inference_precision(eval_precision()) -- an enclosing bf16 scope, else MNK_EVAL_PRECISION;
-    the precision is part of the program key, so a changed scope or variable captures a program of its own instead of replaying
-    the other form.  The same holds for ops.eval_norm_fusion(eval_fuse_norm()): an enclosing scope, else MNK_EVAL_FUSE_NORM, and for
-    ops.eval_skinny_conv(eval_skinny()): an enclosing scope, else MNK_EVAL_SKINNY."""
+    The forward is captured inside ops.eval_options(*eval_options()) -- per field an enclosing scope, else MNK_EVAL_PRECISION /
+    MNK_EVAL_FUSE_NORM / MNK_EVAL_SKINNY; the value is part of the program key, so a changed scope or variable captures a program
+    of its own instead of replaying another form."""
 
     MAX_PROGRAMS = 8
 
@@ -507,14 +506,14 @@ class EvalRunner:
         key = self._flatten((inputs, kwargs), flat)
         if not flat or any(t.dtype != torch.float32 for _, t in flat):
             return NotImplemented
-        precision, fuse, skinny = eval_precision(), eval_fuse_norm(), eval_skinny()
-        key = (precision, fuse, skinny, key)
+        opts = eval_options()
+        key = (opts, key)
         fp = self._fingerprint(module)
         prog = self.programs.get(key)
         if prog is None or prog["fp"] != fp:
             if len(self.programs) >= self.MAX_PROGRAMS:
                 self.programs.clear()
-            prog = self.programs[key] = self._capture(module, inputs, kwargs, flat, device, fp, precision, fuse, skinny)
+            prog = self.programs[key] = self._capture(module, inputs, kwargs, flat, device, fp, opts)
         dsts, srcs = [], []
         for i, ((path, t), s) in enumerate(zip(flat, prog["static"])):
             if t.device.type == "cpu" and not t.is_pinned():
@@ -552,14 +551,14 @@ class EvalRunner:
         ring["buf"][k].copy_(t)
         return ring["buf"][k], ring["ev"][k]
 
-    def _capture(self, module, inputs, kwargs, flat, device, fp, precision="fp32", fuse=False, skinny=False):
+    def _capture(self, module, inputs, kwargs, flat, device, fp, opts):
         static = [t.to(device).clone() for _, t in flat]
         leaves = {path: s for (path, _), s in zip(flat, static)}
         s_in, s_kw = self._rebuild((inputs, kwargs), leaves)
         cap = torch.cuda.Stream()
         cap.wait_stream(torch.cuda.current_stream())
         # (the caches are keyed by stream: fill them on the stream the capture runs on)
-        with torch.cuda.stream(cap), mops.inference_precision(precision), mops.eval_norm_fusion(fuse), mops.eval_skinny_conv(skinny):
+        with torch.cuda.stream(cap), mops.eval_options(*opts):
             for _ in range(2):
                 module(*s_in, **s_kw)
         torch.cuda.current_stream().wait_stream(cap)
@@ -567,13 +566,15 @@ class EvalRunner:
         graph = torch.cuda.CUDAGraph()
         mops.FROZEN_CAPTURE[0] = True
         try:
-            with torch.cuda.graph(graph, stream=cap), mops.inference_precision(precision), mops.eval_norm_fusion(fuse), \
-                    mops.eval_skinny_conv(skinny):
+            with torch.cuda.graph(graph, stream=cap), mops.eval_options(*opts):
                 out = module(*s_in, **s_kw)
         finally:
             mops.FROZEN_CAPTURE[0] = False
         self.stats["captures"] += 1
-        return {"graph": graph, "static": static, "out": out, "fp": fp}
+        # the graph reads the cached evaluation-mode norm coefficients by address, and that cache keeps ONE entry per layer, keyed by
+        # the stream among others: the warm-up of the next program (a stream of its own) replaces it.  The program holds what it reads
+        coeffs = [mops._BN_EVAL.get(id(b)) for b in module.buffers()]
+        return {"graph": graph, "static": static, "out": out, "fp": fp, "coeffs": coeffs}
 
 
 def _clone_all(obj):
@@ -597,24 +598,22 @@ def _walk_clone(obj):
     return obj
 
 
-def eval_precision():
-    """the precision of an evaluation-mode forward behind DataParallelWithCallback: the enclosing ops.inference_precision scope
-    where it is not fp32 (a wrapper handed to Reconstructor(precision="bf16") or called inside the scope), else MNK_EVAL_PRECISION.
-    The captured program and the eager fall-backs (MNK_EVAL_GRAPH=0, a signature the runner declines) both use it."""
-    scope = mops.current_precision()
-    return scope if scope != "fp32" else mops.check_precision(knobs.get("MNK_EVAL_PRECISION"))
+# (field of ops.EvalOptions, environment switch, its parser)
+_EVAL_KNOBS = (("precision", "MNK_EVAL_PRECISION", lambda name: mops.check_precision(knobs.get(name))),
+               ("fuse_norm", "MNK_EVAL_FUSE_NORM", knobs.on),
+               ("skinny", "MNK_EVAL_SKINNY", knobs.on))
+_EVAL_DEFAULT = mops.EvalOptions()
+assert tuple(f for f, _, _ in _EVAL_KNOBS) == _EVAL_DEFAULT._fields
 
 
-def eval_fuse_norm():
-    """whether an evaluation-mode forward behind DataParallelWithCallback runs inside ops.eval_norm_fusion: an enclosing scope that
-    is on, else MNK_EVAL_FUSE_NORM.  Like eval_precision it is part of the captured program's key and the eager fall-backs use it."""
-    return bool(mops.current_norm_fusion() or knobs.on("MNK_EVAL_FUSE_NORM"))
-
-
-def eval_skinny():
-    """whether an evaluation-mode forward behind DataParallelWithCallback runs inside ops.eval_skinny_conv: an enclosing scope that
-    is on, else MNK_EVAL_SKINNY.  Part of the captured program's key, and the eager fall-backs use it, like eval_fuse_norm."""
-    return bool(mops.current_skinny_conv() or knobs.on("MNK_EVAL_SKINNY"))
+def eval_options():
+    """The ops.EvalOptions of an evaluation-mode forward behind DataParallelWithCallback, per field: the enclosing ops.eval_options
+    scope where it says something other than the default (a wrapper handed to Reconstructor(precision="bf16"), or called inside
+    ops.inference_precision / eval_norm_fusion / eval_skinny_conv), else the field's environment switch.  The captured program (the
+    value is part of its key) and the eager fall-backs (MNK_EVAL_GRAPH=0, a signature the runner declines) both use it."""
+    scope = mops.current_eval_options()
+    return mops.EvalOptions(*[getattr(scope, f) if getattr(scope, f) != getattr(_EVAL_DEFAULT, f) else parse(name)
+                              for f, name, parse in _EVAL_KNOBS])
 
 
 def eval_runner_for(wrapper):

@@ -572,9 +572,8 @@ class Reconstructor:
 
     def __init__(self, kp_detector, generator, use_graph=False, precision="fp32", fuse_norm=False, skinny=False):
         self.kp_detector, self.generator = kp_detector.eval(), generator.eval()
-        self.precision = mops.check_precision(precision)
-        self.fuse_norm = bool(fuse_norm)
-        self.skinny = bool(skinny)
+        self.options = mops.EvalOptions(mops.check_precision(precision), bool(fuse_norm), bool(skinny))
+        self.precision, self.fuse_norm, self.skinny = self.options
         self.use_graph = bool(use_graph)
         self._graph = None
         self._static_in = None
@@ -582,7 +581,7 @@ class Reconstructor:
 
     @torch.no_grad()
     def _forward(self, source, driving):
-        with mops.inference_precision(self.precision), mops.eval_norm_fusion(self.fuse_norm), mops.eval_skinny_conv(self.skinny):
+        with mops.eval_options(*self.options):
             kp_source = self.kp_detector(source)
             kp_driving = self.kp_detector(driving)
             out = self.generator(source, kp_driving=kp_driving, kp_source=kp_source)
@@ -661,15 +660,13 @@ class Transfer:
     def __init__(self, kp_detector, generator, normalization_params, shared_source=False, precision="fp32", fuse_norm=False,
                  skinny=False):
         self.kp_detector, self.generator = kp_detector.eval(), generator.eval()
-        self.precision = mops.check_precision(precision)
-        self.fuse_norm = bool(fuse_norm)
-        self.skinny = bool(skinny)
+        self.options = mops.EvalOptions(mops.check_precision(precision), bool(fuse_norm), bool(skinny))
+        self.precision, self.fuse_norm, self.skinny = self.options
         self.params = dict(normalization_params)
         self.shared_source = bool(shared_source)
 
     def __call__(self, source_image, driving_video):
-        with torch.no_grad(), mops.inference_precision(self.precision), mops.eval_norm_fusion(self.fuse_norm), \
-                mops.eval_skinny_conv(self.skinny):
+        with torch.no_grad(), mops.eval_options(*self.options):
             return self._run(source_image, driving_video)
 
     def _run(self, source_image, driving_video):

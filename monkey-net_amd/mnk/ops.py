@@ -399,30 +399,39 @@ _FORMS = {
 }
 
 
-def _packed_fwd_weight(weight, cout, c0, c1, up=False):
-    """Packed [Cout][chunk][tap][16] copy of a conv weight for NO-GRAD forwards (inference loops), cached per parameter
-    version, storage and optimiser epoch.  Training forwards never use this cache (they take the registry entry of
-    _pack_entry: re-packed once per iteration by repack_registered(), or per call in a user-owned loop).
-    Under hipGraph capture the cache is bypassed: the pack launch is recorded INTO the graph (its buffer lives in the
-    graph's memory pool), so every replay re-packs from the live parameter -- a replay after load_state_dict / an
-    in-place write can never combine old packed weights with new normalisation parameters."""
-    form = _FORMS["up" if up else "3x3"]
-    n, pack = _query(form.packed, cout, c0, c1), form.pack
+def _cached_pack(kind, weight, shape, nfloats, make):
+    """One cached pack of a conv weight for NO-GRAD forwards: `make(wp)` launches the pack into a fresh buffer of `nfloats`.
+    kind: "fwd" or "up" (one entry per parameter: `up` is part of the stored shape, so either form replaces the other) or
+    ("skinny", bf16) (an entry of its own per precision).  An entry is valid for one parameter version, storage and optimiser
+    epoch and dies with its parameter.  Under hipGraph capture the cache is bypassed: the pack launch is recorded INTO the graph
+    (its buffer lives in the graph's memory pool), so every replay re-packs from the live parameter -- a replay after
+    load_state_dict / an in-place write can never combine old packed weights with new normalisation parameters.  (A capture with
+    frozen weights, FROZEN_CAPTURE, takes the cached pack and records its address.)"""
     if weight.is_cuda and torch.cuda.is_current_stream_capturing() and not FROZEN_CAPTURE[0]:
-        wp = torch.empty(n, dtype=torch.float32, device=weight.device)
-        _call(pack, weight, _p(weight), _p(wp), cout, c0, c1)
+        wp = torch.empty(nfloats, dtype=torch.float32, device=weight.device)
+        make(wp)
         return wp
-    key = (id(weight), weight.device)
+    key = (id(weight), weight.device, "fwd" if kind == "up" else kind)
     ver = (weight._version, _PACK_EPOCH[0], weight.data_ptr())
+    shape = (kind, shape)
     hit = _PACK_CACHE.get(key)
-    if hit is not None and hit[0] == ver and hit[1] == (cout, c0, c1, up) and hit[3]() is weight:
+    if hit is not None and hit[0] == ver and hit[1] == shape and hit[3]() is weight:
         return hit[2]
-    wp = torch.empty(n, dtype=torch.float32, device=weight.device)
-    _call(pack, weight, _p(weight), _p(wp), cout, c0, c1)
+    wp = torch.empty(nfloats, dtype=torch.float32, device=weight.device)
+    make(wp)
     if hit is None:
         weakref.finalize(weight, _PACK_CACHE.pop, key, None)      # no entry (and no packed buffer) outlives its parameter
-    _PACK_CACHE[key] = (ver, (cout, c0, c1, up), wp, weakref.ref(weight))
+    _PACK_CACHE[key] = (ver, shape, wp, weakref.ref(weight))
     return wp
+
+
+def _packed_fwd_weight(weight, cout, c0, c1, up=False):
+    """Packed [Cout][chunk][tap][16] copy of a conv weight for NO-GRAD forwards (inference loops), cached by _cached_pack.
+    Training forwards never use this cache (they take the registry entry of _pack_entry: re-packed once per iteration by
+    repack_registered(), or per call in a user-owned loop)."""
+    form = _FORMS["up" if up else "3x3"]
+    return _cached_pack("up" if up else "fwd", weight, (cout, c0, c1), _query(form.packed, cout, c0, c1),
+                        lambda wp: _call(form.pack, weight, _p(weight), _p(wp), cout, c0, c1))
 
 
 def up1x1_dead_taps(n, hs, ws):
@@ -604,6 +613,18 @@ _SplitPending = namedtuple("_SplitPending", "ws splits phases bias")
 _NO_SPLIT = _SplitPending(None, 0, 1, None)      # what a BatchNorm with nothing pending tells its kernel
 
 
+def _drop_stale_split_pending():
+    """Before a launch that may use the scratch workspace: the BatchNorm of an earlier deferred split-K convolution never ran -- an
+    exception between the two launches (the entry is popped by that BatchNorm; nothing else may run in between).  The partial sums
+    are gone with the scratch buffer; drop the entry -- a retry of the forward pass must not be poisoned by the failed one -- and
+    say so."""
+    if _SPLIT_PENDING:
+        import warnings
+        warnings.warn("dropping the deferred split-K partial sums of %d convolution(s) whose BatchNorm never ran (an "
+                      "exception between a convolution and its normalisation layer?)" % len(_SPLIT_PENDING))
+        _SPLIT_PENDING.clear()
+
+
 def _small_sync(rows):
     """several ranks with the peer-to-peer exchange up: a small layer's backward is mnk_bn_small_bwd_sync (one launch)"""
     return mdist.active() and 1 < rows <= _query("mnk_bn_small_rows") and _sync_handle() is not None
@@ -627,14 +648,7 @@ def _gemm_launch(form, x0, c0, x1, c1, wp, bias, residual, n, h, w, cout, flags=
     bn: the _BnRecord of the BatchNorm in front of a data gradient, whose backward statistics the launch leaves where its plan
     has a statistics form (else an ordinary launch).  kxk: (hi, wi, kh, kw, pad) of the "kxk" form."""
     f = _FORMS[form]
-    if _SPLIT_PENDING:
-        # the BatchNorm of an earlier deferred split-K convolution never ran: an exception between the two launches (the entry
-        # is popped by that BatchNorm; nothing else may run in between).  The partial sums are gone with the scratch buffer;
-        # drop the entry -- a retry of the forward pass must not be poisoned by the failed one -- and say so
-        import warnings
-        warnings.warn("dropping the deferred split-K partial sums of %d convolution(s) whose BatchNorm never ran (an "
-                      "exception between a convolution and its normalisation layer?)" % len(_SPLIT_PENDING))
-        _SPLIT_PENDING.clear()
+    _drop_stale_split_pending()
     up = form == "up"
     y = torch.empty(n, h * 2 if up else h, w * 2 if up else w, ceil4(cout), dtype=torch.float32, device=x0.device)
     size = (n, h, w, c0, cout) if form == "up_dgrad" else (n, h, w, c0, c1, cout, kxk[2] * kxk[3]) if kxk else (n, h, w, c0, c1, cout)
@@ -686,38 +700,64 @@ def bf16_excluded(cin, cout):
     spread 0.021).  The narrower key-point heat-map head (35 -> 10; 1.16 ... 1.24 x, outside the gate's range) keeps the flag."""
     return cout <= 16 and cin >= 64
 
-_PRECISION = ["fp32"]
-
-
 def check_precision(precision):
     if precision not in PRECISIONS:
         raise ValueError("precision must be one of %s, not %r" % (PRECISIONS, precision))
     return precision
 
 
-class inference_precision:
-    """Context manager: inside `with inference_precision("bf16"):` every 3x3 and sub-pixel forward convolution launched under
-    torch.no_grad() runs its products in one bf16 pass.  A convolution called with gradients enabled inside the scope raises
-    RuntimeError: the backward kernels are fp32 and would not differentiate what was computed.  Outside any scope the precision
-    is fp32; the previous value is restored on exit, also after an exception.
-    The precision is one value per process, not per thread: a scope opened in one thread also changes the convolutions another
-    thread launches meanwhile.  The loops here are single-threaded; keep an fp32 forward of another thread out of the scope."""
+# ---- the evaluation options: precision, norm fusion, skinny convolutions ------------------------------------------------------------
+# what a forward launched under torch.no_grad() runs with.  One value per process, not per thread: a scope opened in one thread also
+# changes the convolutions another thread launches meanwhile.  The loops here are single-threaded; keep a default forward of another
+# thread out of a scope.
+EvalOptions = namedtuple("EvalOptions", "precision fuse_norm skinny", defaults=("fp32", False, False))
 
-    def __init__(self, precision):
-        self.precision = check_precision(precision)
+
+class _EvalState:
+    __slots__ = EvalOptions._fields
+
+
+_EVAL = _EvalState()
+_EVAL.precision, _EVAL.fuse_norm, _EVAL.skinny = EvalOptions()
+
+
+def current_eval_options():
+    return EvalOptions(_EVAL.precision, _EVAL.fuse_norm, _EVAL.skinny)
+
+
+class eval_options:
+    """Context manager: `with eval_options(precision="bf16", skinny=True):` sets the given fields (None: the field stays as it is)
+    for the forwards launched inside; `with eval_options(*opts):` sets all three from an EvalOptions.  The previous values of the
+    fields it set are restored on exit, also after an exception.  inference_precision, eval_norm_fusion and eval_skinny_conv
+    (below) are this scope with one field and say what each field does."""
+
+    def __init__(self, precision=None, fuse_norm=None, skinny=None):
+        self.precision = None if precision is None else check_precision(precision)
+        self.fuse_norm = None if fuse_norm is None else bool(fuse_norm)
+        self.skinny = None if skinny is None else bool(skinny)
 
     def __enter__(self):
-        self.previous = _PRECISION[0]
-        _PRECISION[0] = self.precision
+        self.previous = [(f, getattr(_EVAL, f)) for f in EvalOptions._fields if getattr(self, f) is not None]
+        for f, _ in self.previous:
+            setattr(_EVAL, f, getattr(self, f))
         return self
 
     def __exit__(self, *exc):
-        _PRECISION[0] = self.previous
+        for f, v in self.previous:
+            setattr(_EVAL, f, v)
         return False
 
 
+def inference_precision(precision):
+    """Context manager: inside `with inference_precision("bf16"):` every 3x3 and sub-pixel forward convolution launched under
+    torch.no_grad() runs its products in one bf16 pass.  A convolution called with gradients enabled inside the scope raises
+    RuntimeError: the backward kernels are fp32 and would not differentiate what was computed.  Outside any scope the precision
+    is fp32."""
+    return eval_options(precision=check_precision(precision))
+
+
 def current_precision():
-    return _PRECISION[0]
+    return _EVAL.precision
 
 
 # ---- opt-in bf16 (mixed-precision) training ---------------------------------------------------------------------------------------
@@ -755,6 +795,18 @@ def current_training_precision():
     return _TRAIN_PRECISION[0]
 
 
+def _fwd_launch_geometry(ups, up, h, w, c0, c1, cout):
+    """-> (hq, wq, flags) of a forward launch on an (h, w) output.  up: the sub-pixel form, whose calls take the LOW resolution and
+    no flags of the view; else bit 0 = nearest x2 up-sampled view, bit 1 = MNK_CONV_CLEAN_PADS -- every act this module produces
+    has zero pad channels (tests/test_modules.py::test_pad_channels_are_written pins that), so the fast 3x3 loader applies.
+    Bit 3 = MNK_CONV_BF16 inside inference_precision("bf16") (conv3x3 vouches for no_grad and an evaluation-mode norm layer), not
+    for bf16_excluded layers: they stay fp32."""
+    hq, wq, flags = (h // 2, w // 2, 0) if up else (h, w, int(bool(ups)) | 2)
+    if _EVAL.precision == "bf16" and not bf16_excluded(c0 + c1, cout):
+        flags |= 8
+    return hq, wq, flags
+
+
 def _conv_launch(x0, c0, x1, c1, ups, wp, bias, residual, n, h, w, cout, want_stats=False, up=False, eval_defer=False,
                  train_bf16=False):
     """One conv launch.  With want_stats the BatchNorm sums of the output come out of the conv epilogue (finished by a
@@ -768,15 +820,11 @@ def _conv_launch(x0, c0, x1, c1, ups, wp, bias, residual, n, h, w, cout, want_st
     # evaluation mode: the norm layer that follows sums a split launch's partials itself
     evald = eval_defer and not want_stats and residual is None and h % 2 == 0 and w % 2 == 0
     assert not up or (ups and residual is None)
-    # flags: bit 0 = nearest x2 up-sampled view, bit 1 = MNK_CONV_CLEAN_PADS -- every act this module produces has zero
-    # pad channels (tests/test_modules.py::test_pad_channels_are_written pins that), so the fast 3x3 loader applies
-    form, hq, wq, flags = ("up", h // 2, w // 2, 0) if up else ("3x3", h, w, int(ups) | 2)
-    # MNK_CONV_BF16 (conv3x3 vouches for no_grad and an evaluation-mode norm layer).  Not for bf16_excluded layers: they stay fp32
+    hq, wq, flags = _fwd_launch_geometry(ups, up, h, w, c0, c1, cout)
     if train_bf16:
-        flags |= 16                          # MNK_CONV_BF16_TRAIN: the node's decision (Conv3x3Fn.forward), statistics allowed
-    elif _PRECISION[0] == "bf16" and not bf16_excluded(c0 + c1, cout):
-        flags |= 8
-    y, st = _gemm_launch(form, x0, c0, x1, c1, wp, bias, residual, n, hq, wq, cout, flags, want_stats and not small, small or evald)
+        flags = flags & ~8 | 16              # MNK_CONV_BF16_TRAIN: the node's decision (Conv3x3Fn.forward), statistics allowed
+    y, st = _gemm_launch("up" if up else "3x3", x0, c0, x1, c1, wp, bias, residual, n, hq, wq, cout, flags, want_stats and not small,
+                         small or evald)
     if small:
         return y, y.new_empty(0)
     sums = None
@@ -1062,7 +1110,6 @@ class Conv3x3SkipFn(_Fn):
 # (mnk_conv3x3_fwd_evalnorm / mnk_conv3x3_up_fwd_evalnorm): z is written once and y never.  Equal to the two launches bit for bit.
 # Where the library's form query answers 0 -- a split plan (the deferred-split hand-over serves it), a pooled layer without a
 # window-major kernel -- and in training, with gradients enabled or with the scope off, everything is what it was.
-_FUSE_NORM = [False]
 # the finished output of a fused launch on its way to the bn_act that the caller runs next: z.data_ptr() -> (z, norm, relu, pool)
 _FUSED_PENDING = {}
 # conv -> evaluation-mode norm pairs (callers that pass `follow`) under no_grad since clear_eval_norm_count():
@@ -1071,25 +1118,13 @@ EVAL_NORM_COUNT = [0, 0, 0, 0]
 _PAIR_PENDING = [None]                    # y.data_ptr() of an unfused pair's convolution, for the count in bn_act
 
 
-class eval_norm_fusion:
-    """Context manager: `with eval_norm_fusion(True):` (see above).  One value per process, like inference_precision; the previous
-    value is restored on exit, also after an exception."""
-
-    def __init__(self, on=True):
-        self.on = bool(on)
-
-    def __enter__(self):
-        self.previous = _FUSE_NORM[0]
-        _FUSE_NORM[0] = self.on
-        return self
-
-    def __exit__(self, *exc):
-        _FUSE_NORM[0] = self.previous
-        return False
+def eval_norm_fusion(on=True):
+    """Context manager: `with eval_norm_fusion(True):` (see above) -- eval_options with this one field."""
+    return eval_options(fuse_norm=bool(on))
 
 
 def current_norm_fusion():
-    return _FUSE_NORM[0]
+    return _EVAL.fuse_norm
 
 
 def clear_eval_norm_count():
@@ -1111,9 +1146,7 @@ def _conv_evalnorm(x0, c0, x1, c1, ups, weight, bias, norm, relu, pool):
     up = subpixel(ups)
     if pool and (up or h % 2 or w % 2):
         return None
-    hq, wq, flags = (h // 2, w // 2, 0) if up else (h, w, int(ups) | 2)          # as _conv_launch
-    if _PRECISION[0] == "bf16" and not bf16_excluded(c0 + c1, cout):
-        flags |= 8
+    hq, wq, flags = _fwd_launch_geometry(ups, up, h, w, c0, c1, cout)
     form = _query("mnk_conv3x3_evalnorm_form", n, hq, wq, c0, c1, cout, flags, int(up), int(pool))
     if not form:
         return None
@@ -1142,30 +1175,16 @@ def _conv_evalnorm(x0, c0, x1, c1, ups, weight, bias, norm, relu, pool):
 # most "skinny_rows") runs as mnk_conv3x3_skinny_fwd on a pack of its own (plain nine taps, bf16 elements under
 # inference_precision("bf16")) and leaves split partials to the norm layer through the deferred split-K hand-over
 # (_SPLIT_PENDING -> mnk_bn_eval_split_fwd).  With gradients enabled, in training, or with the scope off nothing changes.
-_SKINNY = [False]
 EVAL_SKINNY_COUNT = [0]                   # layers that took the form since clear_eval_skinny_count()
-_SKINNY_PACK_CACHE = {}
 
 
-class eval_skinny_conv:
-    """Context manager: `with eval_skinny_conv(True):` (see above).  One value per process, like eval_norm_fusion; the previous
-    value is restored on exit, also after an exception."""
-
-    def __init__(self, on=True):
-        self.on = bool(on)
-
-    def __enter__(self):
-        self.previous = _SKINNY[0]
-        _SKINNY[0] = self.on
-        return self
-
-    def __exit__(self, *exc):
-        _SKINNY[0] = self.previous
-        return False
+def eval_skinny_conv(on=True):
+    """Context manager: `with eval_skinny_conv(True):` (see above) -- eval_options with this one field."""
+    return eval_options(skinny=bool(on))
 
 
 def current_skinny_conv():
-    return _SKINNY[0]
+    return _EVAL.skinny
 
 
 def clear_eval_skinny_count():
@@ -1173,24 +1192,10 @@ def clear_eval_skinny_count():
 
 
 def _packed_skinny_weight(weight, cout, c0, c1, bf16):
-    """The skinny pack of a conv weight (mnk_conv3x3_skinny_pack; bf16: half the bytes), cached like _packed_fwd_weight's -- per
-    parameter version, storage, optimiser epoch AND precision -- and, like it, re-made inside a capture that is not FROZEN_CAPTURE."""
-    n = _query("mnk_conv3x3_skinny_packed_floats", cout, c0, c1, int(bf16))
-    if weight.is_cuda and torch.cuda.is_current_stream_capturing() and not FROZEN_CAPTURE[0]:
-        wp = torch.empty(n, dtype=torch.float32, device=weight.device)
-        _call("mnk_conv3x3_skinny_pack", weight, _p(weight), _p(wp), cout, c0, c1, int(bf16))
-        return wp
-    key = (id(weight), weight.device, bool(bf16))
-    ver = (weight._version, _PACK_EPOCH[0], weight.data_ptr())
-    hit = _SKINNY_PACK_CACHE.get(key)
-    if hit is not None and hit[0] == ver and hit[1] == (cout, c0, c1) and hit[3]() is weight:
-        return hit[2]
-    wp = torch.empty(n, dtype=torch.float32, device=weight.device)
-    _call("mnk_conv3x3_skinny_pack", weight, _p(weight), _p(wp), cout, c0, c1, int(bf16))
-    if hit is None:
-        weakref.finalize(weight, _SKINNY_PACK_CACHE.pop, key, None)
-    _SKINNY_PACK_CACHE[key] = (ver, (cout, c0, c1), wp, weakref.ref(weight))
-    return wp
+    """The skinny pack of a conv weight (mnk_conv3x3_skinny_pack; bf16: half the bytes), cached by _cached_pack per precision."""
+    nfloats = _query("mnk_conv3x3_skinny_packed_floats", cout, c0, c1, int(bf16))
+    return _cached_pack(("skinny", bool(bf16)), weight, (cout, c0, c1), nfloats,
+                        lambda wp: _call("mnk_conv3x3_skinny_pack", weight, _p(weight), _p(wp), cout, c0, c1, int(bf16)))
 
 
 def _conv_skinny(x0, c0, x1, c1, ups, weight, bias, norm, relu, pool):
@@ -1205,16 +1210,11 @@ def _conv_skinny(x0, c0, x1, c1, ups, weight, bias, norm, relu, pool):
     h, w = (hs * 2, ws_ * 2) if ups else (hs, ws_)
     if h % 2 or w % 2:                       # the hand-over's condition (BNActFn.forward)
         return None
-    bf16 = _PRECISION[0] == "bf16" and not bf16_excluded(c0 + c1, cout)
-    flags = int(bool(ups)) | 2 | (8 if bf16 else 0)
+    _, _, flags = _fwd_launch_geometry(ups, False, h, w, c0, c1, cout)       # never the sub-pixel form: the full resolution
     if not _query("mnk_conv3x3_skinny_form", n, h, w, c0, c1, cout, flags, int(bool(pool))):
         return None
-    if _SPLIT_PENDING:
-        import warnings
-        warnings.warn("dropping the deferred split-K partial sums of %d convolution(s) whose BatchNorm never ran (an "
-                      "exception between a convolution and its normalisation layer?)" % len(_SPLIT_PENDING))
-        _SPLIT_PENDING.clear()
-    wp = _packed_skinny_weight(weight, cout, c0, c1, bf16)
+    _drop_stale_split_pending()
+    wp = _packed_skinny_weight(weight, cout, c0, c1, bool(flags & 8))
     size = (n, h, w, c0, c1, cout)
     nws = _query("mnk_conv3x3_skinny_workspace_floats", *size)
     ws = SCRATCH.get("ws", nws, x0)
@@ -1235,25 +1235,25 @@ def conv3x3(x0, c0, weight, bias=None, x1=None, c1=0, ups=False, residual=None, 
     and y is never written.
     follow: (norm, relu, pool) of that bn_act call.  Inside eval_norm_fusion(True) an unsplit launch then applies the layer itself
     and what comes back as `y` is the finished z: the bn_act that follows recognises it and hands it through."""
-    if _PRECISION[0] != "fp32":
+    if _EVAL.precision != "fp32":
         if torch.is_grad_enabled():
             raise RuntimeError("a convolution with gradients enabled inside inference_precision(%r): the backward kernels are "
-                               "fp32 and would not differentiate what was computed -- call it under torch.no_grad()" % _PRECISION[0])
+                               "fp32 and would not differentiate what was computed -- call it under torch.no_grad()" % _EVAL.precision)
         if want_stats:
             raise RuntimeError("inference_precision(%r) is for evaluation-mode networks: a training-mode norm layer asked this "
-                               "convolution for batch statistics" % _PRECISION[0])
+                               "convolution for batch statistics" % _EVAL.precision)
     track = torch.is_grad_enabled() and any(
         t is not None and t.requires_grad for t in (x0, x1, weight, bias, residual))
     eval_defer = bool(eval_bn and not want_stats and residual is None and not torch.is_grad_enabled()
                       and knobs.form("EVAL_SPLIT_FUSED"))
     pair = eval_defer and follow is not None and not follow[0].training
-    if pair and _SKINNY[0]:
+    if pair and _EVAL.skinny:
         # few output rows: the weight-streaming launch; its partials go to the norm layer like a deferred split-K launch's
         y = _conv_skinny(x0, c0, x1, c1, ups, weight, bias, *follow)
         if y is not None:
             _PAIR_PENDING[0] = y.data_ptr()
             return (y, None, x0) if skip else (y, None)
-    if pair and _FUSE_NORM[0]:
+    if pair and _EVAL.fuse_norm:
         # a conv -> evaluation-mode norm pair under no_grad: fused where the scope is on and the library has the form
         z = _conv_evalnorm(x0, c0, x1, c1, ups, weight, bias, *follow)
         if z is not None:

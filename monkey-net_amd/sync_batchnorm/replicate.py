@@ -138,13 +138,11 @@ class DataParallelWithCallback(nn.Module):
                 if out is not NotImplemented:
                     return out
             if not torch.is_grad_enabled():
-                # the eager fall-backs (MNK_EVAL_GRAPH=0, a signature the runner declines) in the precision the runner would have
-                # captured in: MNK_EVAL_PRECISION, or the enclosing scope (with gradients enabled the variable does not apply);
-                # likewise MNK_EVAL_FUSE_NORM
+                # the eager fall-backs (MNK_EVAL_GRAPH=0, a signature the runner declines) with the options the runner would have
+                # captured with: the enclosing scope, else the MNK_EVAL_* variables (with gradients enabled they do not apply)
                 from mnk import ops as mops
                 inputs, kwargs = self._scatter(inputs, kwargs, dev)
-                with mops.inference_precision(dropin.eval_precision()), mops.eval_norm_fusion(dropin.eval_fuse_norm()), \
-                        mops.eval_skinny_conv(dropin.eval_skinny()):
+                with mops.eval_options(*dropin.eval_options()):
                     return self.module(*_to_device(inputs, dev), **_to_device(kwargs, dev))
         inputs, kwargs = self._scatter(inputs, kwargs, dev)
         return self.module(*_to_device(inputs, dev), **_to_device(kwargs, dev))

@@ -279,3 +279,174 @@ def test_an_exception_inside_a_convolution_call_leaves_no_hand_over_behind(be, m
         with pytest.raises(RuntimeError, match="pack failed"):
             ops.conv3x3(x, 8, w, None, eval_bn=True)
     assert ops.handover_state() == {}
+
+
+def test_eval_options_scope_sets_and_restores_per_field():
+    """mnk.ops.eval_options: None leaves a field alone, given fields are validated before anything changes, exit restores exactly
+    the fields the scope set (also after an exception), and the three one-field managers share its state."""
+    from mnk import ops
+    default = ops.EvalOptions()
+    assert default == ("fp32", False, False) and ops.current_eval_options() == default
+    with ops.eval_options(skinny=True):
+        assert ops.current_eval_options() == ("fp32", False, True)
+        with ops.eval_options(precision="bf16"):
+            assert ops.current_eval_options() == ("bf16", False, True)
+            with ops.eval_options(fuse_norm=True, skinny=False):
+                assert ops.current_eval_options() == ("bf16", True, False)
+                with ops.eval_options():
+                    assert ops.current_eval_options() == ("bf16", True, False)
+                with ops.eval_options(*default):
+                    assert ops.current_eval_options() == default
+                assert ops.current_eval_options() == ("bf16", True, False)
+            assert ops.current_eval_options() == ("bf16", False, True)
+        assert ops.current_eval_options() == ("fp32", False, True)
+        with pytest.raises(ZeroDivisionError):
+            with ops.eval_options(precision="bf16", fuse_norm=True, skinny=False):
+                assert ops.current_eval_options() == ("bf16", True, False)
+                1 / 0
+        assert ops.current_eval_options() == ("fp32", False, True)
+        with pytest.raises(ValueError):
+            ops.eval_options(precision="fp16", fuse_norm=True)
+        assert ops.current_eval_options() == ("fp32", False, True)
+        # the one-field managers and eval_options observe each other's state
+        with ops.inference_precision("bf16") as scope:
+            assert scope.precision == "bf16"
+            assert ops.current_eval_options() == ("bf16", False, True)
+            assert (ops.current_precision(), ops.current_norm_fusion(), ops.current_skinny_conv()) == ("bf16", False, True)
+            with ops.eval_norm_fusion(True), ops.eval_skinny_conv(False):
+                assert ops.current_eval_options() == ("bf16", True, False)
+                with ops.eval_options(precision="fp32"):
+                    assert ops.current_precision() == "fp32" and ops.current_norm_fusion() is True
+            assert ops.current_eval_options() == ("bf16", False, True)
+    assert ops.current_eval_options() == default
+    with pytest.raises(ValueError):
+        ops.inference_precision("fp16")
+    with pytest.raises(AttributeError):
+        ops.current_eval_options().precision = "bf16"          # what callers get is a value, not the state
+
+
+KNOB_OF = {"precision": ("MNK_EVAL_PRECISION", "bf16"), "fuse_norm": ("MNK_EVAL_FUSE_NORM", "1"), "skinny": ("MNK_EVAL_SKINNY", "1")}
+
+
+@pytest.mark.parametrize("field", ["precision", "fuse_norm", "skinny"])
+def test_dropin_eval_options_takes_the_scope_first_and_the_variable_otherwise(monkeypatch, field):
+    """mnk.dropin.eval_options(), per field: the enclosing scope where it says something other than the default, else the
+    environment variable -- the rule of the three functions it replaces (precision: the scope if it is not "fp32", else
+    MNK_EVAL_PRECISION; switches: the scope if it is on, else the variable set to 1)."""
+    from mnk import dropin, ops
+    for name, _ in KNOB_OF.values():
+        monkeypatch.delenv(name, raising=False)
+    default = ops.EvalOptions()
+    other = {"precision": "bf16", "fuse_norm": True, "skinny": True}[field]
+    changed = default._replace(**{field: other})
+    name, value = KNOB_OF[field]
+    assert dropin.eval_options() == default
+    with ops.eval_options(**{field: other}):                   # the scope alone
+        assert dropin.eval_options() == changed
+    with ops.eval_options(**{field: getattr(default, field)}):
+        assert dropin.eval_options() == default
+    monkeypatch.setenv(name, value)                            # the variable alone
+    assert dropin.eval_options() == changed
+    with ops.eval_options(**{field: getattr(default, field)}):  # a scope that says the default does not hide the variable
+        assert dropin.eval_options() == changed
+    with ops.eval_options(**{field: other}):                   # both
+        assert dropin.eval_options() == changed
+    monkeypatch.setenv(name, {"precision": "fp32"}.get(field, "0"))
+    assert dropin.eval_options() == default
+    with ops.eval_options(**{field: other}):                   # the scope has precedence over a variable that says the default
+        assert dropin.eval_options() == changed
+    if field == "precision":
+        monkeypatch.setenv(name, "fp16")
+        with pytest.raises(ValueError):
+            dropin.eval_options()
+    assert ops.current_eval_options() == default
+
+
+@pytest.mark.gpu
+def test_eval_runner_keeps_one_program_per_options_value(monkeypatch):
+    """(The emulator runs on CPU tensors and cannot capture a graph.)  The tiny detector behind DataParallelWithCallback, one
+    frame per call under no_grad, with each of the 2 x 2 x 2 settings of the MNK_EVAL_* variables: eight programs, keyed by the
+    options, none evicted (EvalRunner.MAX_PROGRAMS = 8); a second round replays all eight, each to the frame of its first call."""
+    import itertools
+    import weakref
+    from conftest import Backend
+    from sync_batchnorm import DataParallelWithCallback
+    from mnk import dropin, ops
+    be = Backend("hip")
+    gold = load("tiny")
+    gen, kpd = _models(gold, be)
+    kp_detector = DataParallelWithCallback(kpd)
+    kp_detector.eval()
+    _, drv = cases.smooth_pair(1, gold["size"], gold["size"])
+    drv = be.t(drv)
+    combos = list(itertools.product(("fp32", "bf16"), ("0", "1"), ("0", "1")))
+    assert dropin.EvalRunner.MAX_PROGRAMS == len(combos) == 8
+    handed, coeffs = [], ops._bn_eval_coeffs
+
+    def spy(*args):
+        out = coeffs(*args)
+        if ops.FROZEN_CAPTURE[0]:               # cached norm coefficients whose addresses a capture records
+            handed.extend(weakref.ref(t) for t in out)
+        return out
+
+    monkeypatch.setattr(ops, "_bn_eval_coeffs", spy)
+    first = {}
+    with torch.no_grad():
+        for rnd in range(2):
+            for combo in combos:
+                for name, value in zip(("MNK_EVAL_PRECISION", "MNK_EVAL_FUSE_NORM", "MNK_EVAL_SKINNY"), combo):
+                    monkeypatch.setenv(name, value)
+                out = kp_detector(drv)["mean"].clone()
+                torch.cuda.synchronize()
+                assert torch.equal(out, first.setdefault(combo, out)), combo
+            runner = dropin.eval_runner_for_wrapper(kp_detector)
+            assert runner.stats == {"captures": 8, "replays": 8 * (rnd + 1)}, (rnd, runner.stats)
+    # what a program's graph reads by address lives as long as the program, whatever later captures put into the caches
+    assert handed and all(r() is not None for r in handed)
+    assert sorted(k[0] for k in runner.programs) == sorted(ops.EvalOptions(p, f == "1", s == "1") for p, f, s in combos)
+    assert not torch.equal(first[("fp32", "0", "0")], first[("bf16", "0", "0")])
+    assert ops.current_eval_options() == ops.EvalOptions() and ops.handover_state() == {}
+
+
+def test_one_pack_cache_holds_the_forward_and_both_skinny_packs_of_a_weight(be, monkeypatch):
+    """ops._PACK_CACHE: a weight's forward pack, fp32 skinny pack and bf16 skinny pack are three entries; a repeated call returns
+    the cached tensor without a pack launch; a new epoch re-makes all three in place; all three die with the weight."""
+    import gc
+    from mnk import ops
+    w = torch.nn.Parameter(be.t(torch.randn(5, 4, 1, 3, 3) * 0.3))
+    packs = []
+    call = ops._call
+
+    def counting(name, *args):
+        if "pack" in name:
+            packs.append(name)
+        return call(name, *args)
+
+    monkeypatch.setattr(ops, "_call", counting)
+
+    def all_three():
+        with torch.no_grad():
+            return (ops._packed_fwd_weight(w, 5, 4, 0), ops._packed_skinny_weight(w, 5, 4, 0, False),
+                    ops._packed_skinny_weight(w, 5, 4, 0, True))
+
+    gc.collect()
+    n0 = len(ops._PACK_CACHE)
+    made = all_three()
+    assert len(ops._PACK_CACHE) == n0 + 3
+    assert packs == ["mnk_conv3x3_pack_fwd", "mnk_conv3x3_skinny_pack", "mnk_conv3x3_skinny_pack"]
+    assert len({t.data_ptr() for t in made}) == 3
+    again = all_three()
+    assert all(a is b for a, b in zip(made, again)) and len(packs) == 3
+    ops.invalidate_packed_weights()                            # bumps _PACK_EPOCH: every pack is stale
+    fresh = all_three()
+    assert len(packs) == 6 and len(ops._PACK_CACHE) == n0 + 3
+    assert all(a is not b for a, b in zip(made, fresh)) and all(a is b for a, b in zip(fresh, all_three()))
+    be.sync()
+    assert all(torch.equal(a, b) for a, b in zip(made, fresh))
+    # the sub-pixel pack of the same weight takes the forward entry's place (one forward entry per parameter)
+    with torch.no_grad():
+        up = ops._packed_fwd_weight(w, 5, 4, 0, True)
+    assert len(ops._PACK_CACHE) == n0 + 3 and up is not fresh[0] and packs[-1] == "mnk_conv3x3_up_pack_fwd"
+    del w
+    gc.collect()
+    assert len(ops._PACK_CACHE) == n0

@@ -52,49 +52,62 @@ def alternate(forms, iters, reps):
     return {k: {"ms": round(sorted(v)[len(v) // 2], 4), "spread_ms": round(max(v) - min(v), 4)} for k, v in times.items()}
 
 
-def reconstructor_ab(config, batch, size, iters):
+def reconstructor_ab(config, batch, size, iters, field, values, precision="fp32", extras=None):
+    """Reconstructor(precision=precision, field=value) for each of values = {form: value}, the baseline first, alternating;
+    extras(res, recs, src, drv) adds what the A/B reports besides the timings"""
     gen, disc, kpd = bench.build_models(configs.get(config), dev)
     src = torch.rand(batch, 3, 1, size, size, device=dev)
     drv = torch.rand(batch, 3, 1, size, size, device=dev)
-    recs = {p: engine.Reconstructor(kpd, gen, precision=p) for p in ("fp32", "bf16")}
-    res = alternate({p: (lambda r=r: r(src, drv)) for p, r in recs.items()}, iters, args.reps)
-    a, b = recs["fp32"](src, drv)["video_prediction"], recs["bf16"](src, drv)["video_prediction"]
-    res["max_abs_prediction_difference"] = float((a - b).abs().max())
-    return {"workload": "%s Reconstructor eager, batch %d @ %dx%d" % (config, batch, size, size), **res,
-            "speedup": round(res["fp32"]["ms"] / res["bf16"]["ms"], 3)}
+    recs = {f: engine.Reconstructor(kpd, gen, **{"precision": precision, field: v}) for f, v in values.items()}
+    res = alternate({f: (lambda r=r: r(src, drv)) for f, r in recs.items()}, iters, args.reps)
+    if extras:
+        extras(res, recs, src, drv)
+    base, other = values
+    tag = "" if field == "precision" else " %s," % precision
+    return {"workload": "%s Reconstructor eager,%s batch %d @ %dx%d" % (config, tag, batch, size, size), **res,
+            "speedup": round(res[base]["ms"] / res[other]["ms"], 3)}
 
 
-def frame_loop_ab(config, size, frames, iters):
-    """reconstruction.py:45-62: both networks behind DataParallelWithCallback, one frame per call under no_grad"""
+def frame_loop_ab(config, size, frames, iters, variable, values, precision=None, extras=None):
+    """reconstruction.py:45-62: both networks behind DataParallelWithCallback, one frame per call under no_grad, with the
+    environment `variable` alternating over values = {form: value}, the baseline first (precision: MNK_EVAL_PRECISION of both);
+    extras(res, last) adds what the A/B reports besides the timings, last = {form: the last prediction}"""
     from sync_batchnorm import DataParallelWithCallback
     gen, disc, kpd = bench.build_models(configs.get(config), dev)
     generator, kp_detector = DataParallelWithCallback(gen), DataParallelWithCallback(kpd)
     generator.eval(), kp_detector.eval()
     video = torch.rand(1, 3, frames, size, size, device=dev)
-
-    def loop(precision):
+    if precision:
         os.environ["MNK_EVAL_PRECISION"] = precision
+    last = {}
+
+    def loop(form):
+        os.environ[variable] = values[form]
         with torch.no_grad():
             kp_source = kp_detector(video[:, :, :1])
             for i in range(frames):
                 kp_driving = kp_detector(video[:, :, i:i + 1])
-                generator(source_image=video[:, :, :1], kp_driving=kp_driving, kp_source=kp_source)
+                last[form] = generator(source_image=video[:, :, :1], kp_driving=kp_driving, kp_source=kp_source)["video_prediction"]
 
-    res = alternate({p: (lambda p=p: loop(p)) for p in ("fp32", "bf16")}, iters, args.reps)
-    os.environ.pop("MNK_EVAL_PRECISION", None)
-    for v in (res["fp32"], res["bf16"]):
-        v["ms_per_frame"] = round(v["ms"] / frames, 4)
-    return {"workload": "%s frame loop through EvalRunner, batch 1 @ %dx%d, %d frames per loop" % (config, size, size, frames), **res,
-            "speedup": round(res["fp32"]["ms"] / res["bf16"]["ms"], 3)}
+    res = alternate({f: (lambda f=f: loop(f)) for f in values}, iters, args.reps)
+    if extras:
+        extras(res, last)
+    os.environ.pop(variable, None); os.environ.pop("MNK_EVAL_PRECISION", None)
+    base, other = values
+    for f in values:
+        res[f]["ms_per_frame"] = round(res[f]["ms"] / frames, 4)
+    tag = " %s," % precision if precision else ""
+    return {"workload": "%s frame loop through EvalRunner,%s batch 1 @ %dx%d, %d frames per loop" % (config, tag, size, size, frames), **res,
+            "speedup": round(res[base]["ms"] / res[other]["ms"], 3)}
 
 
-def reconstructor_fuse_ab(config, batch, size, iters, precision):
+def precision_extras(res, recs, src, drv):
+    a, b = recs["fp32"](src, drv)["video_prediction"], recs["bf16"](src, drv)["video_prediction"]
+    res["max_abs_prediction_difference"] = float((a - b).abs().max())
+
+
+def fuse_extras(res, recs, src, drv):
     from mnk import _lib, ops
-    gen, disc, kpd = bench.build_models(configs.get(config), dev)
-    src = torch.rand(batch, 3, 1, size, size, device=dev)
-    drv = torch.rand(batch, 3, 1, size, size, device=dev)
-    recs = {f: engine.Reconstructor(kpd, gen, precision=precision, fuse_norm=(f == "fused")) for f in ("default", "fused")}
-    res = alternate({f: (lambda r=r: r(src, drv)) for f, r in recs.items()}, iters, args.reps)
     a, b = recs["default"](src, drv), recs["fused"](src, drv)
     res["outputs_equal"] = all(torch.equal(a[k], b[k]) for k in a)
     for f, r in recs.items():
@@ -105,89 +118,38 @@ def reconstructor_fuse_ab(config, batch, size, iters, precision):
         res[f]["groups"] = {k: {"launches": round(v["launches_per_step"], 1), "ms": round(v["ms_per_step"], 4)}
                             for k, v in groups.items() if k in ("conv3x3_igemm", "bn_act_apply", "conv3x3_reduce_pack")}
         res[f]["all_groups_ms"] = round(sum(v["ms_per_step"] for v in groups.values()), 4)
-    return {"workload": "%s Reconstructor eager, %s, batch %d @ %dx%d" % (config, precision, batch, size, size), **res,
-            "speedup": round(res["default"]["ms"] / res["fused"]["ms"], 3)}
 
 
-def frame_loop_fuse_ab(config, size, frames, iters, precision):
-    """frame_loop_ab with MNK_EVAL_FUSE_NORM alternating"""
-    from sync_batchnorm import DataParallelWithCallback
-    gen, disc, kpd = bench.build_models(configs.get(config), dev)
-    generator, kp_detector = DataParallelWithCallback(gen), DataParallelWithCallback(kpd)
-    generator.eval(), kp_detector.eval()
-    video = torch.rand(1, 3, frames, size, size, device=dev)
-    os.environ["MNK_EVAL_PRECISION"] = precision
-
-    def loop(fuse):
-        os.environ["MNK_EVAL_FUSE_NORM"] = fuse
-        with torch.no_grad():
-            kp_source = kp_detector(video[:, :, :1])
-            for i in range(frames):
-                kp_driving = kp_detector(video[:, :, i:i + 1])
-                generator(source_image=video[:, :, :1], kp_driving=kp_driving, kp_source=kp_source)
-
-    res = alternate({f: (lambda v=v: loop(v)) for f, v in (("default", "0"), ("fused", "1"))}, iters, args.reps)
-    os.environ.pop("MNK_EVAL_FUSE_NORM", None); os.environ.pop("MNK_EVAL_PRECISION", None)
-    for v in (res["default"], res["fused"]):
-        v["ms_per_frame"] = round(v["ms"] / frames, 4)
-    return {"workload": "%s frame loop through EvalRunner, %s, batch 1 @ %dx%d, %d frames per loop" % (config, precision, size, size, frames),
-            **res, "speedup": round(res["default"]["ms"] / res["fused"]["ms"], 3)}
-
-
-def reconstructor_skinny_ab(config, batch, size, iters, precision):
+def skinny_extras(res, recs, src, drv):
     from mnk import ops
-    gen, disc, kpd = bench.build_models(configs.get(config), dev)
-    src = torch.rand(batch, 3, 1, size, size, device=dev)
-    drv = torch.rand(batch, 3, 1, size, size, device=dev)
-    recs = {f: engine.Reconstructor(kpd, gen, precision=precision, skinny=(f == "skinny")) for f in ("default", "skinny")}
-    res = alternate({f: (lambda r=r: r(src, drv)) for f, r in recs.items()}, iters, args.reps)
     a, b = recs["default"](src, drv), recs["skinny"](src, drv)
     res["max_abs_output_difference"] = max(float((a[k] - b[k]).abs().max()) for k in a)
     ops.clear_eval_skinny_count()
     recs["skinny"](src, drv)
     res["skinny_layers"] = ops.EVAL_SKINNY_COUNT[0]
-    return {"workload": "%s Reconstructor eager, %s, batch %d @ %dx%d" % (config, precision, batch, size, size), **res,
-            "speedup": round(res["default"]["ms"] / res["skinny"]["ms"], 3)}
 
 
-def frame_loop_skinny_ab(config, size, frames, iters, precision):
-    """frame_loop_ab with MNK_EVAL_SKINNY alternating"""
-    from sync_batchnorm import DataParallelWithCallback
+def skinny_loop_extras(res, last):
     from mnk import ops
-    gen, disc, kpd = bench.build_models(configs.get(config), dev)
-    generator, kp_detector = DataParallelWithCallback(gen), DataParallelWithCallback(kpd)
-    generator.eval(), kp_detector.eval()
-    video = torch.rand(1, 3, frames, size, size, device=dev)
-    os.environ["MNK_EVAL_PRECISION"] = precision
-    last = {}
-
-    def loop(value):
-        os.environ["MNK_EVAL_SKINNY"] = value
-        with torch.no_grad():
-            kp_source = kp_detector(video[:, :, :1])
-            for i in range(frames):
-                kp_driving = kp_detector(video[:, :, i:i + 1])
-                last[value] = generator(source_image=video[:, :, :1], kp_driving=kp_driving, kp_source=kp_source)["video_prediction"]
-
-    ops.clear_eval_skinny_count()
-    res = alternate({f: (lambda v=v: loop(v)) for f, v in (("default", "0"), ("skinny", "1"))}, iters, args.reps)
     res["skinny_layers_captured"] = ops.EVAL_SKINNY_COUNT[0]      # counted while the programs were captured (warm-up + capture passes)
-    res["max_abs_prediction_difference"] = float((last["0"] - last["1"]).abs().max())
-    os.environ.pop("MNK_EVAL_SKINNY", None); os.environ.pop("MNK_EVAL_PRECISION", None)
-    for v in (res["default"], res["skinny"]):
-        v["ms_per_frame"] = round(v["ms"] / frames, 4)
-    return {"workload": "%s frame loop through EvalRunner, %s, batch 1 @ %dx%d, %d frames per loop" % (config, precision, size, size, frames),
-            **res, "speedup": round(res["default"]["ms"] / res["skinny"]["ms"], 3)}
+    res["max_abs_prediction_difference"] = float((last["default"] - last["skinny"]).abs().max())
 
 
+def frame_loop_skinny_ab(*job):
+    from mnk import ops
+    ops.clear_eval_skinny_count()
+    return frame_loop_ab(*job, "MNK_EVAL_SKINNY", {"default": "0", "skinny": "1"}, precision, skinny_loop_extras)
+
+
+FUSED, SKINNY = {"default": False, "fused": True}, {"default": False, "skinny": True}
 if args.skinny_ab:
     only = set(filter(None, args.only.split(",")))
     for precision in ("fp32", "bf16"):
-        jobs = [("frame-loop", lambda: frame_loop_skinny_ab("moving-gif", 64, 16, max(2, args.iters // 2), precision)),
-                ("frame-loop-taichi", lambda: frame_loop_skinny_ab("taichi", 64, 16, max(2, args.iters // 2), precision)),
-                ("frame-loop-vox", lambda: frame_loop_skinny_ab("vox", 256, 8, max(2, args.iters // 2), precision)),
-                ("bair", lambda: reconstructor_skinny_ab("bair", 512, 64, args.iters, precision)),
-                ("moving-gif", lambda: reconstructor_skinny_ab("moving-gif", 64, 64, args.iters, precision))]
+        jobs = [("frame-loop", lambda: frame_loop_skinny_ab("moving-gif", 64, 16, max(2, args.iters // 2))),
+                ("frame-loop-taichi", lambda: frame_loop_skinny_ab("taichi", 64, 16, max(2, args.iters // 2))),
+                ("frame-loop-vox", lambda: frame_loop_skinny_ab("vox", 256, 8, max(2, args.iters // 2))),
+                ("bair", lambda: reconstructor_ab("bair", 512, 64, args.iters, "skinny", SKINNY, precision, skinny_extras)),
+                ("moving-gif", lambda: reconstructor_ab("moving-gif", 64, 64, args.iters, "skinny", SKINNY, precision, skinny_extras))]
         for name, job in jobs:
             if not only or name in only:
                 print(json.dumps(job()), flush=True)
@@ -196,10 +158,11 @@ if args.skinny_ab:
 if args.fuse_ab:
     only = set(filter(None, args.only.split(",")))
     for precision in ("fp32", "bf16"):
-        jobs = [("bair", lambda: reconstructor_fuse_ab("bair", 512, 64, args.iters, precision)),
-                ("moving-gif", lambda: reconstructor_fuse_ab("moving-gif", 64, 64, args.iters, precision)),
-                ("vox", lambda: reconstructor_fuse_ab("vox", 8, 256, max(2, args.iters // 2), precision)),
-                ("frame-loop", lambda: frame_loop_fuse_ab("moving-gif", 64, 16, max(2, args.iters // 2), precision))]
+        jobs = [("bair", lambda: reconstructor_ab("bair", 512, 64, args.iters, "fuse_norm", FUSED, precision, fuse_extras)),
+                ("moving-gif", lambda: reconstructor_ab("moving-gif", 64, 64, args.iters, "fuse_norm", FUSED, precision, fuse_extras)),
+                ("vox", lambda: reconstructor_ab("vox", 8, 256, max(2, args.iters // 2), "fuse_norm", FUSED, precision, fuse_extras)),
+                ("frame-loop", lambda: frame_loop_ab("moving-gif", 64, 16, max(2, args.iters // 2), "MNK_EVAL_FUSE_NORM",
+                                                     {"default": "0", "fused": "1"}, precision))]
         for name, job in jobs:
             if not only or name in only:
                 print(json.dumps(job()), flush=True)
@@ -207,10 +170,11 @@ if args.fuse_ab:
 
 if args.precision_ab:
     only = set(filter(None, args.only.split(",")))
-    jobs = [("bair", lambda: reconstructor_ab("bair", 512, 64, args.iters)),
-            ("moving-gif", lambda: reconstructor_ab("moving-gif", 64, 64, args.iters)),
-            ("vox", lambda: reconstructor_ab("vox", 8, 256, max(2, args.iters // 2))),
-            ("frame-loop", lambda: frame_loop_ab("moving-gif", 64, 16, max(2, args.iters // 2)))]
+    forms = {"fp32": "fp32", "bf16": "bf16"}
+    jobs = [("bair", lambda: reconstructor_ab("bair", 512, 64, args.iters, "precision", forms, extras=precision_extras)),
+            ("moving-gif", lambda: reconstructor_ab("moving-gif", 64, 64, args.iters, "precision", forms, extras=precision_extras)),
+            ("vox", lambda: reconstructor_ab("vox", 8, 256, max(2, args.iters // 2), "precision", forms, extras=precision_extras)),
+            ("frame-loop", lambda: frame_loop_ab("moving-gif", 64, 16, max(2, args.iters // 2), "MNK_EVAL_PRECISION", forms))]
     for name, job in jobs:
         if not only or name in only:
             print(json.dumps(job()), flush=True)
