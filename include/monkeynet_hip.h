@@ -948,6 +948,37 @@ int mnk_gru_head_fwd(const float* y, long rows, int num_kp, int feats, int has_v
 int mnk_gru_head_bwd(const float* y, const float* dmean, const float* dvar, long rows, int num_kp, int feats, int has_var, float* dy,
                      void* stream);
 
+/* ---- the prediction task around its GRU (prediction.py:28-32,94-133; csrc/predict.hip) -----------------------------------
+ * A key-point ROW is one frame of the predictor's input (prediction_module.py:28-33): I = K * 2 floats, all means [K][2], or with
+ * 'var' I = K * 6: all means, then all covariances [K][2][2].  The linear layer's output row y is interleaved per key point:
+ * [K][feats], feats = 2 or 6 (m0 m1 v00 v01 v10 v11); the head entries below map between the two orders.  No atomics: every sum
+ * has a fixed order, two runs are bit-identical. */
+/* KPDataset.__getitem__ + the DataLoader's collation + .cuda() + the gt clones + the masking (prediction.py:28-32,97-100), and
+ * with starts[b] = b * T the roll-out's masking (prediction.py:121-122), in one launch: gt[b][t] = pool row starts[b] + t (pool
+ * [rows][ld], ld >= I; starts: B row indices in DEVICE memory), x[b][t] = the same row for t < init_frames and zeros behind.
+ * A row index outside [0, rows) is not read: its row of gt (and of x) is NaN. */
+int mnk_kp_window_gather(const float* pool, long rows, long ld, const int64_t* starts, int B, int T, int init_frames, int I, float* x,
+                         float* gt, void* stream);
+/* prediction_module.py:33-42 + prediction.py:103 without the predicted key points in memory: y [B * T][K * feats], gt [B * T][I]
+ * (a row per (b, t)) -> loss[0] = mean |gt_mean - tanh(y_mean)| over the frames t >= init_frames (+ with has_var, feats = 6:
+ * mean |gt_var - V^T V|, each mean over its own element count).  Two launches: per-block partial sums into ws
+ * (mnk_gru_head_l1_workspace_floats), then one block that adds them in index order.  epoch_acc (may be NULL; DEVICE [2] = running
+ * sum, iteration count, zeroed by the caller when an epoch starts): one thread adds the loss, in iteration order; loss_log (may be
+ * NULL, log_cap floats) receives the loss at index `iteration count` when that is below log_cap. */
+size_t mnk_gru_head_l1_workspace_floats(int B, int T, int K);
+int mnk_gru_head_l1_fwd(const float* y, const float* gt, int B, int T, int K, int feats, int has_var, int init_frames, float* loss,
+                        float* epoch_acc, float* loss_log, int log_cap, float* ws, size_t ws_floats, void* stream);
+/* the gradient of that loss (upstream gradient 1) with respect to y: -sign(gt - p) / count (sign(0) = 0, as torch.abs) through
+ * 1 - p^2 for the means and dV = V (G + G^T) for the covariances (the autograd of prediction.py:103,105 through
+ * prediction_module.py:33-42); rows of the frames t < init_frames are zeros */
+int mnk_gru_head_l1_bwd(const float* y, const float* gt, int B, int T, int K, int feats, int has_var, int init_frames, float* dy,
+                        void* stream);
+/* prediction.py:127-131 on the predictor's output mean [B][T][K][2] / var [B][T][K][2][2] (NULL without has_var), in place:
+ * frames t < init_frames take kp_init's rows ([B * T][ld] in row order); with predict_variance and has_var EVERY frame's
+ * covariance becomes that of frame init_frames - 1 -- the reference's meaning of the flag: set = copied, not predicted */
+int mnk_kp_rollout_finish(const float* kp_init, long ld, int B, int T, int K, int has_var, int init_frames, int predict_variance,
+                          float* mean, float* var, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

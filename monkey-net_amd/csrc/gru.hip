@@ -17,6 +17,7 @@
 //   gru_colsum        bias gradients: column sums in a fixed order (two stages)
 // No floating-point atomics, no persistent kernel, no grid-wide barrier.
 #include "mnk_common.h"
+#include "gru_head.h"
 
 using namespace mnk;
 
@@ -329,16 +330,8 @@ __global__ void __launch_bounds__(256) gru_head_fwd_kernel(const float* __restri
     const long e = (long)blockIdx.x * 256 + threadIdx.x;        // (row, key point)
     if (e >= n) return;
     const float* v = y + e * F;
-    mean[2 * e] = tanhf(v[0]);
-    mean[2 * e + 1] = tanhf(v[1]);
-    if (has_var) {                                              // V = [[v2, v3], [v4, v5]], var = V^T V
-        const float a = v[2], b = v[3], c = v[4], d = v[5];
-        float* o = var + 4 * e;
-        o[0] = a * a + c * c;
-        o[1] = a * b + c * d;
-        o[2] = a * b + c * d;
-        o[3] = b * b + d * d;
-    }
+    head_mean(v, mean[2 * e], mean[2 * e + 1]);
+    if (has_var) head_var(v, var + 4 * e);                      // (the per-key-point formulas: gru_head.h)
 }
 
 __global__ void __launch_bounds__(256) gru_head_bwd_kernel(const float* __restrict__ y, const float* __restrict__ dmean,
@@ -350,19 +343,11 @@ __global__ void __launch_bounds__(256) gru_head_bwd_kernel(const float* __restri
     float* o = dy + e * F;
     for (int f = 0; f < F; ++f) o[f] = 0.f;
     if (dmean) {
-        const float m0 = tanhf(v[0]), m1 = tanhf(v[1]);
-        o[0] = dmean[2 * e] * (1.f - m0 * m0);
-        o[1] = dmean[2 * e + 1] * (1.f - m1 * m1);
+        float m0, m1;
+        head_mean(v, m0, m1);
+        head_mean_bwd(dmean[2 * e], dmean[2 * e + 1], m0, m1, o);
     }
-    if (has_var && dvar) {                                      // dV = V (G + G^T)
-        const float* g = dvar + 4 * e;
-        const float s00 = 2.f * g[0], s01 = g[1] + g[2], s11 = 2.f * g[3];
-        const float a = v[2], b = v[3], c = v[4], d = v[5];
-        o[2] = a * s00 + b * s01;
-        o[3] = a * s01 + b * s11;
-        o[4] = c * s00 + d * s01;
-        o[5] = c * s01 + d * s11;
-    }
+    if (has_var && dvar) head_var_bwd(v, dvar + 4 * e, o);      // dV = V (G + G^T)
 }
 
 // ---- column sums (bias gradients) ------------------------------------------------------------------------------------------

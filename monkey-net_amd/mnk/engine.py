@@ -685,3 +685,6 @@ class Transfer:
         unfold = lambda t: t.reshape(b, d, c, h, w).permute(0, 2, 1, 3, 4)       # (B*d, C, 1, H, W) -> (B, C, d, H, W)
         return {"video_prediction": unfold(out["video_prediction"]), "video_deformed": unfold(out["video_deformed"]),
                 "kp_driving": kp_driving, "kp_source": kp_source, "kp_norm": kp_norm}
+
+
+from .prediction import Prediction, KeyPointPool  # noqa: E402,F401  (the fourth run mode's engine: mnk/prediction.py)

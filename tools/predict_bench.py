@@ -10,7 +10,14 @@ warm-up, each timing closed by a device synchronise.
 Prints one JSON line: median milliseconds of both forms for both shapes, and the training iteration's algorithmic GFLOP over time
 against the 157.3 TFLOP/s fp32 matrix peak.
 
-  python tools/predict_bench.py [--iters 20] [--warmup 3] [--batch 256] [--frames 32] [--hidden 1024] [--num-kp 10]"""
+With --engine the line also carries train_ms_engine_eager / train_ms_engine_graph: mnk.engine.Prediction.fit on a device-resident
+key-point pool (window gather, forward, the L1 loss fused with the head, backward, MnkAdam; eager launches / one hipGraph replay
+per iteration), timed in the same alternation as one fit() of --engine-epochs epochs of --engine-iters iterations -- window
+draws, the epoch mean read by the host and the scheduler step included -- divided by the iterations.  (The windows of an epoch
+are drawn on the host while the device works on the epoch before; only the first epoch's draws of a fit() are exposed.)  Its
+yard-stick is train_ms_native of the same run.
+
+  python tools/predict_bench.py [--iters 20] [--warmup 3] [--batch 256] [--frames 32] [--hidden 1024] [--num-kp 10] [--engine]"""
 import argparse
 import json
 import os
@@ -68,6 +75,9 @@ def main():
     ap.add_argument("--hidden", type=int, default=1024)
     ap.add_argument("--num-kp", type=int, default=10)
     ap.add_argument("--init-frames", type=int, default=1)
+    ap.add_argument("--engine", action="store_true", help="also time mnk.engine.Prediction.fit, eager and as hipGraph replay")
+    ap.add_argument("--engine-iters", type=int, default=4, help="iterations per epoch of the engine forms")
+    ap.add_argument("--engine-epochs", type=int, default=8, help="epochs per timed fit() of the engine forms")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("predict_bench.py times the GPU: no device found")
@@ -121,8 +131,29 @@ def main():
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) * 1e3
 
+    engines = {}
+    if a.engine:
+        from mnk.engine import Prediction, KeyPointPool
+        videos = a.engine_iters * B
+        rows = torch.cat([torch.cat([v.reshape(B * T, -1) for v in batch(B).values()], -1) for _ in range(a.engine_iters)])
+        pool = KeyPointPool(rows.contiguous(), [(i * T, T) for i in range(videos)])
+        params = {"rnn_params": {"num_features": H, "num_layers": 1, "dropout": 0}, "predict_variance": True, "num_epochs": 1,
+                  "lr": 1e-3, "batch_size": B, "num_frames": T, "init_frames": a.init_frames, "train_size": None}
+        for form, graph in (("engine_eager", False), ("engine_graph", True)):
+            eng = Prediction(None, None, params, num_kp=K, kp_variance="matrix", use_graph=graph)
+            eng.predictor.load_state_dict(native.state_dict())
+            engines[form] = eng
+
+    def engine_epoch(form):
+        engines[form].fit(pool, num_epochs=a.engine_epochs)
+
     times = {(w, n): [] for w in ("train", "infer") for n in mods}
+    times.update({("train", form): [] for form in engines})
     for i in range(a.warmup + a.iters):
+        for form in (sorted(engines) if i % 2 == 0 else sorted(engines, reverse=True)):
+            ms = timed(engine_epoch, form) / (a.engine_iters * a.engine_epochs)
+            if i >= a.warmup:
+                times[("train", form)].append(ms)
         for w, fn in (("train", train_iter), ("infer", infer)):
             for n in (("native", "stock") if i % 2 == 0 else ("stock", "native")):
                 ms = timed(fn, n)
@@ -143,6 +174,10 @@ def main():
         "train_speedup": round(med[("train", "stock")] / med[("train", "native")], 3),
         "infer_speedup": round(med[("infer", "stock")] / med[("infer", "native")], 3),
     }
+    for form in engines:
+        res["train_ms_" + form] = round(med[("train", form)], 3)
+    if engines:
+        res["engine_iters_per_epoch"], res["engine_epochs_per_fit"] = a.engine_iters, a.engine_epochs
     print(json.dumps(res))
 
 
