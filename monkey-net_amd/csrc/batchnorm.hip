@@ -23,6 +23,9 @@ struct Map2D {
 static int g_bn_rpt = tuning_knob("bn_rpt", &g_bn_rpt, 4);            // rows per thread before a layer is cut (A/B: 8 -> 4: 11.51 -> 11.44 ms per step)
 static int g_bn_blocks = tuning_knob("bn_blocks", &g_bn_blocks, 1024);   // into more row blocks; block cap
 static int g_bn_exact_tx = tuning_knob("bn_exact_tx", &g_bn_exact_tx, 1);   // 0: power-of-two quad lanes per block (rounds 1-5)
+// the forward apply's map (no reduction there: small layers want blocks, not rows per thread)
+static int g_bn_fwd_rpt = tuning_knob("bn_fwd_rpt", &g_bn_fwd_rpt, 2);
+static int g_bn_fwd_blocks = tuning_knob("bn_fwd_blocks", &g_bn_fwd_blocks, 2048);
 
 static Map2D make_map(long rows, int ld, int rows_per_thread = 0, int want_blocks = 0) {
     if (rows_per_thread <= 0) rows_per_thread = g_bn_rpt;
@@ -72,7 +75,78 @@ __device__ __forceinline__ float4 ld4_guard(const float* p, int q, int C) {
     return v;
 }
 
+// ld4_guard without a branch around the loads (for use inside a row loop): a lane beyond C reads the last channel and drops it
+__device__ __forceinline__ float4 ld4_clamp(const float* p, int q, int C) {
+    const int c = q * 4, last = C - 1;
+    const float x = p[c < last ? c : last], y = p[c + 1 < last ? c + 1 : last], z = p[c + 2 < last ? c + 2 : last],
+                w = p[c + 3 < last ? c + 3 : last];
+    return make_float4(c < C ? x : 0.f, c + 1 < C ? y : 0.f, c + 2 < C ? z : 0.f, c + 3 < C ? w : 0.f);
+}
+
+// a + b that stays an addition of its own where a is a product (never contracted into a multiply-add)
+__device__ __forceinline__ float4 f4_add_exact(float4 a, float4 b) {
+#pragma clang fp contract(off)
+    return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+}
+
+constexpr int ROWS_IN_FLIGHT = 4;
+
+// The row walk of one thread -- r, r + step, r + 2 * step, ... below r1 -- with the global loads of R consecutive rows of the walk in
+// flight: fetch(e, row) issues the loads of row slot e and nothing else, use(e, row) does the arithmetic and the stores of that
+// slot; all R fetches come before the first use, and the uses run in row order, so every sum a thread keeps adds its rows in the
+// order of a one-row loop.  (One row at a time the loops were a load, s_waitcnt vmcnt(0), arithmetic, store chain: a dependent
+// memory round trip per row and input, about 16 KB in flight per CU.)  The loop of full batches has no branch.  The last 1 ... R - 1
+// rows are one more batch whose missing slots load the last row that exists -- a row from r1 on is never loaded -- and are not used.
+// MNK_LOADS_ISSUED: a line the compiler moves no load across (it costs no instruction and waits for nothing; the pointers loaded
+// from are not __restrict__: a load from read-only no-alias memory may cross it).  Without it a load whose value only a
+// conditional use needs -- a slot of the last batch -- is sunk into that condition, behind the wait for the slots in front of it
+#ifdef HIPEMU
+#define MNK_LOADS_ISSUED() ((void)0)
+#else
+#define MNK_LOADS_ISSUED() asm volatile("" ::: "memory")
+#endif
+// ... and MNK_USED_AFTER_LOADS(quad), placed behind the loads: the arithmetic that reads this register quad (a channel constant
+// every row is combined with first) stays behind that line as well.  Pure arithmetic is not held by the line above, and to save
+// registers the scheduler pulls the arithmetic of the first slot -- and the wait for its loads -- in front of the loads of the
+// other slots where a slot is several loads (the pooled forward form)
+#ifdef HIPEMU
+#define MNK_USED_AFTER_LOADS(q) ((void)0)
+#define MNK_USED_AFTER_LOADS1(x) ((void)0)
+#else
+#define MNK_USED_AFTER_LOADS1(x) asm volatile("" : "+v"(x) : : "memory")
+#define MNK_USED_AFTER_LOADS(q) asm volatile("" : "+v"((q).x), "+v"((q).y), "+v"((q).z), "+v"((q).w) : : "memory")
+#endif
+struct NoTie {
+    __device__ __forceinline__ void operator()() const {}
+};
+// issued(): called behind the loads of a batch (for MNK_USED_AFTER_LOADS)
+template <int R, class Fetch, class Use, class Issued = NoTie>
+__device__ __forceinline__ void walk_rows(long r, long r1, int step, Fetch fetch, Use use, Issued issued = Issued()) {
+    for (; r + (long)(R - 1) * step < r1; r += (long)R * step) {
+#pragma unroll
+        for (int e = 0; e < R; ++e) fetch(e, r + (long)e * step);
+        MNK_LOADS_ISSUED();
+        issued();
+#pragma unroll
+        for (int e = 0; e < R; ++e) use(e, r + (long)e * step);
+    }
+    if (R > 1 && r < r1) {
+        int n = 1;
+#pragma unroll
+        for (int e = 1; e < R - 1; ++e) n += r + (long)e * step < r1;
+#pragma unroll
+        for (int e = 0; e < R - 1; ++e) fetch(e, r + (long)(e < n ? e : n - 1) * step);
+        MNK_LOADS_ISSUED();
+        issued();
+#pragma unroll
+        for (int e = 0; e < R - 1; ++e)
+            if (e < n) use(e, r + (long)e * step);
+    }
+}
+
 // partial[rb][which][ld]
+// F: fetch(r, q, raw) = the loads of row r, finish(raw, consts, q, a, b) = its two summands; the channel constants of a block are
+// loaded once in front of the loop (per-frame statistics: blockIdx.z is the frame of every row of the block)
 template <class F>
 __global__ void __launch_bounds__(256) colsum2_partial_kernel(F f, long rows, int nv, int ld, int tx_n, int ty_n,
                                                               long rows_per_block, float* __restrict__ partial) {
@@ -86,15 +160,22 @@ __global__ void __launch_bounds__(256) colsum2_partial_kernel(F f, long rows, in
     if (r1 > fbase + rows) r1 = fbase + rows;
     float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
     if (q < nv && ty < ty_n) {        // (ty >= ty_n: the left-over threads of a map whose tx_n does not divide 256)
-        typename F::State st;         // per-thread channel constants (the column quad q is fixed per thread)
-        f.init(st);
-#pragma unroll 2
-        for (long r = r0 + ty; r < r1; r += ty_n) {
-            float4 va, vb;
-            f(r, q, st, va, vb);
-            a = f4_add(a, va);
-            b = f4_add(b, vb);
-        }
+        typename F::Consts k;         // per-thread channel constants (the column quad q is fixed per thread)
+        f.init(k, q, (int)blockIdx.z);
+        typename F::Raw w[F::ROWS];
+        walk_rows<F::ROWS>(
+            r0 + ty, r1, ty_n, [&](int e, long r) { f.fetch(r, q, w[e]); },
+            [&](int e, long) {
+                float4 va, vb;
+                f.finish(w[e], k, q, va, vb);
+                a = f4_add(a, va);
+                b = f4_add(b, vb);
+            },
+            [&]() {
+                MNK_USED_AFTER_LOADS(a);
+                MNK_USED_AFTER_LOADS(b);
+                f.issued(k, w);
+            });
     }
     red[0][threadIdx.x] = a;
     red[1][threadIdx.x] = b;
@@ -274,12 +355,29 @@ static int launch_final_sync(const char* who, void* p2p, const float* partial, i
 struct StatsLoader {
     const float* x;
     int ld;
-    struct State {};
-    __device__ __forceinline__ void init(State&) const {}
-    __device__ __forceinline__ void operator()(long r, int q, State&, float4& a, float4& b) const {
-        a = *reinterpret_cast<const float4*>(x + r * ld + q * 4);
+    struct Consts {};
+    typedef float4 Raw;
+    // one row at a time, as before: with four rows in flight this kernel measured no faster (7.9 us before and after on the 1024-block
+    // layers, the family within its run-to-run spread: profiles/bn_rows_in_flight_ab.txt)
+    static constexpr int ROWS = 1;
+    __device__ __forceinline__ void init(Consts&, int, int) const {}
+    __device__ __forceinline__ void fetch(long r, int q, Raw& w) const { w = *reinterpret_cast<const float4*>(x + r * ld + q * 4); }
+    __device__ __forceinline__ void issued(Consts&, Raw*) const {}
+    __device__ __forceinline__ void finish(const Raw& w, const Consts&, int, float4& a, float4& b) const {
+        a = w;
         b = make_float4(a.x * a.x, a.y * a.y, a.z * a.z, a.w * a.w);
     }
+};
+
+// BwdLoader's row in two halves: what fetch loads ...
+struct BwdRaw {
+    float4 v, d;          // y; dz (the four lanes of the quad, unscaled)
+    float k;              // 1, or the pooled row's 1/4 (0 where an odd row / column is not pooled)
+};
+// ... and the channel constants finish needs
+struct BwdConsts {
+    float4 m, is, sc, be;
+    int rem;              // channels of the thread's quad, 1 ... 4 and more
 };
 
 // g = act'((y-mean)*scale+beta) * dz (dz at half resolution, /4, when pooled); xhat = (y-mean)*invstd
@@ -336,9 +434,80 @@ struct BwdLoader {
         }
         xhat = make_float4(d.x * st.is.x, d.y * st.is.y, d.z * st.is.z, d.w * st.is.w);
     }
-    __device__ __forceinline__ void operator()(long r, int q, State& st, float4& a, float4& b) const {
+    // load() for the row loops that keep several rows in flight (walk_rows), in its parts and without a branch: consts = the
+    // channel constants at statistics offset po, fetch = the loads of row r, finish = load()'s arithmetic, to the bit.
+    // POOL / DZV: the block-uniform cases of load() -- pooled dz; ld_dz and dz_off multiples of four: dz is read as a quad (the
+    // quad of the last channels may reach into the row's next channels, never past the row: dz_off + round_up(C, 4) <= ld_dz
+    // then; those lanes are dropped) -- otherwise lane by lane, a lane beyond C reading the last channel
+    __device__ __forceinline__ void consts(long po, int q, BwdConsts& c) const {
+        c.m = ld4_clamp(mean + po, q, C);
+        c.is = ld4_clamp(invstd + po, q, C);
+        c.sc = ld4_clamp(scale + po, q, C);
+        c.be = ld4_clamp(beta, q, C);
+        c.rem = C - q * 4;
+    }
+    template <bool POOL, bool DZV>
+    __device__ __forceinline__ void fetch(long r, int q, BwdRaw& w) const {
+        w.v = *reinterpret_cast<const float4*>(y + r * ld_y + q * 4);
+        long rz = r;
+        w.k = 1.f;
+        if (POOL) {
+            const unsigned ur = (unsigned)r, t = ur / (unsigned)W;
+            const int wx = (int)(ur - t * (unsigned)W);
+            const unsigned n = t / (unsigned)H;
+            const int h = (int)(t - n * (unsigned)H);
+            rz = ((long)n * (H / 2) + (h >> 1)) * (W / 2) + (wx >> 1);
+            w.k = ((h >> 1) < H / 2 && (wx >> 1) < W / 2) ? 0.25f : 0.f;   // odd H / W: the last row / column is not pooled
+            if (w.k == 0.f) rz = 0;
+        }
+        const float* dp = dz + rz * ld_dz + dz_off + q * 4;
+        if (DZV) {
+            w.d = *reinterpret_cast<const float4*>(dp);
+        } else {
+            const int last = C - q * 4 - 1;        // >= 0: the quads end at round_up(C, 4)
+            w.d = make_float4(dp[0], dp[last < 1 ? last : 1], dp[last < 2 ? last : 2], dp[last < 3 ? last : 3]);
+        }
+    }
+    // behind the loads of a batch of R rows: what finish combines a loaded value with first (MNK_USED_AFTER_LOADS)
+    template <bool POOL, int R>
+    __device__ __forceinline__ void issued(BwdConsts& c, BwdRaw* w) const {
+        MNK_USED_AFTER_LOADS(c.m);
+        MNK_USED_AFTER_LOADS1(c.rem);
+        if (POOL) {
+#pragma unroll
+            for (int e = 0; e < R; ++e) MNK_USED_AFTER_LOADS1(w[e].k);
+        }
+    }
+    __device__ __forceinline__ void finish(const BwdRaw& w, const BwdConsts& c, int q, float4& g, float4& xhat) const {
+        const int rem = c.rem;
+        g = make_float4(rem > 0 ? w.d.x * w.k : 0.f, rem > 1 ? w.d.y * w.k : 0.f, rem > 2 ? w.d.z * w.k : 0.f,
+                        rem > 3 ? w.d.w * w.k : 0.f);
+        const float4 d = make_float4(w.v.x - c.m.x, w.v.y - c.m.y, w.v.z - c.m.z, w.v.w - c.m.w);
+        // (slope < 0, no activation: every lane keeps its factor 1 -- a select, no branch)
+        const float4 pre = make_float4(fmaf(d.x, c.sc.x, c.be.x), fmaf(d.y, c.sc.y, c.be.y), fmaf(d.z, c.sc.z, c.be.z),
+                                       fmaf(d.w, c.sc.w, c.be.w));
+        const bool act = slope >= 0.f;
+        g.x = (act & !(pre.x > 0.f)) ? g.x * slope : g.x;
+        g.y = (act & !(pre.y > 0.f)) ? g.y * slope : g.y;
+        g.z = (act & !(pre.z > 0.f)) ? g.z * slope : g.z;
+        g.w = (act & !(pre.w > 0.f)) ? g.w * slope : g.w;
+        xhat = make_float4(d.x * c.is.x, d.y * c.is.y, d.z * c.is.z, d.w * c.is.w);
+    }
+};
+
+// BwdLoader as colsum2_partial_kernel's row source: the summands g and g * xhat
+template <bool POOL, bool DZV>
+struct BwdRows {
+    BwdLoader L;
+    typedef BwdConsts Consts;
+    typedef BwdRaw Raw;
+    static constexpr int ROWS = DZV ? ROWS_IN_FLIGHT : 3;     // (lane by lane a row of dz is four loads: 128 registers hold three rows)
+    __device__ __forceinline__ void init(Consts& c, int q, int frame) const { L.consts((long)frame * L.pstride, q, c); }
+    __device__ __forceinline__ void fetch(long r, int q, Raw& w) const { L.fetch<POOL, DZV>(r, q, w); }
+    __device__ __forceinline__ void issued(Consts& c, Raw* w) const { L.issued<POOL, ROWS>(c, w); }
+    __device__ __forceinline__ void finish(const Raw& w, const Consts& c, int q, float4& a, float4& b) const {
         float4 g, xh;
-        load(r, q, st, g, xh);
+        L.finish(w, c, q, g, xh);
         a = g;
         b = make_float4(g.x * xh.x, g.y * xh.y, g.z * xh.z, g.w * xh.w);
     }
@@ -488,8 +657,25 @@ struct FwdFinalize {
     int update_running;
 };
 
-template <int POOL, bool FIN = false>
-__global__ void __launch_bounds__(256) bn_act_fwd_kernel(const float* __restrict__ y, int ld_y,
+// z's quad store.  ST (block-uniform, chosen by the host): 0 = lane by lane (z_off or ld_z no multiple of four); 1 = as a quad
+// everywhere (z is a plain act that owns its pad channels -- the guarded parameter loads make the pad lanes of `o` zero -- or C is a
+// multiple of four); 2 = as a quad except the thread of the last, partial quad, whose pad lanes belong to z's next channels
+template <int ST>
+__device__ __forceinline__ void store_quad(float* zp, float4 o, int rem) {
+    if (ST == 1 || (ST == 2 && rem >= 4)) {
+        *reinterpret_cast<float4*>(zp) = o;
+    } else {
+        if (rem > 0) zp[0] = o.x;
+        if (rem > 1) zp[1] = o.y;
+        if (rem > 2) zp[2] = o.z;
+        if (rem > 3) zp[3] = o.w;
+    }
+}
+
+// PF: per-frame statistics (InstanceNorm; pstride = C): the constants of a row are loaded with the row, unconditionally
+template <int POOL, bool FIN, bool PF, int ST>
+__global__ void __launch_bounds__(256) bn_act_fwd_kernel(const float* y, int ld_y,   // (y, addend: not __restrict__ --
+                                                         // a load from read-only no-alias memory may cross MNK_LOADS_ISSUED)
                                                          const float* __restrict__ mean,
                                                          const float* __restrict__ scale,
                                                          const float* __restrict__ beta, int pstride,
@@ -506,11 +692,11 @@ __global__ void __launch_bounds__(256) bn_act_fwd_kernel(const float* __restrict
     const long r0 = (long)blockIdx.y * rows_per_block;
     long r1 = r0 + rows_per_block;
     if (r1 > rows) r1 = rows;
-    const bool vec_store = ((z_off & 3) == 0) && ((ld_z & 3) == 0);
-    const bool owns_pads = z_off == 0 && ld_z == nv * 4;   // z is a plain act: its pad channels are written (as zero) here
     const int rem = C - q * 4;
-    long cur = -1;
-    float4 m = make_float4(0.f, 0.f, 0.f, 0.f), sc = m;
+    // (pooled with per-frame statistics: four loads and two constant quads per row -- two rows fill the 128 registers of four blocks per CU)
+    constexpr int R = (POOL && PF) ? 2 : ROWS_IN_FLIGHT, NK = PF ? R : 1, NPX = POOL ? 4 : 1;
+    float4 m[NK], sc[NK];
+    m[0] = sc[0] = make_float4(0.f, 0.f, 0.f, 0.f);
     const float4 be = ld4_guard(beta, q, C);
     if (FIN) {
         float mm[4] = {0.f, 0.f, 0.f, 0.f}, ss[4] = {0.f, 0.f, 0.f, 0.f};
@@ -528,48 +714,64 @@ __global__ void __launch_bounds__(256) bn_act_fwd_kernel(const float* __restrict
                 if (fin.update_running) bn_update_running(fin.running_mean, fin.running_var, c, fin.momentum, st, fin.count);
             }
         }
-        m = make_float4(mm[0], mm[1], mm[2], mm[3]);
-        sc = make_float4(ss[0], ss[1], ss[2], ss[3]);
-        cur = 0;
+        m[0] = make_float4(mm[0], mm[1], mm[2], mm[3]);
+        sc[0] = make_float4(ss[0], ss[1], ss[2], ss[3]);
+    } else if (!PF) {
+        m[0] = ld4_guard(mean, q, C);
+        sc[0] = ld4_guard(scale, q, C);
     }
-#pragma unroll 2
-    for (long p = r0 + ty; p < r1; p += ty_n) {
-        const long po = pstride ? (long)((unsigned)p / HWo) * pstride : 0;     // per-frame statistics (InstanceNorm)
-        if (!FIN && po != cur) {
-            cur = po;
-            m = ld4_guard(mean + po, q, C);
-            sc = ld4_guard(scale + po, q, C);
-        }
-        float4 o;
-        if (POOL) {
-            const unsigned up = (unsigned)p, t = up / (unsigned)Wo;
-            const int wo = (int)(up - t * (unsigned)Wo);
-            const unsigned n = t / (unsigned)Ho;
-            const int ho = (int)(t - n * (unsigned)Ho);
-            const float* yb = y + (((long)n * H + 2 * ho) * W + 2 * wo) * ld_y + q * 4;
-            o = bn_apply4_pool([=](int dy, int dx) { return ld4_window(yb, W, ld_y, dy, dx); }, m, sc, be, slope);
-        } else {
-            o = bn_apply4(*reinterpret_cast<const float4*>(y + p * ld_y + q * 4), m, sc, be, slope);
-        }
-        float* zp = z + p * ld_z + z_off + q * 4;
-        if (vec_store && (rem >= 4 || owns_pads)) {   // guarded parameter loads make the pad lanes of `o` zero
-            *reinterpret_cast<float4*>(zp) = o;
-        } else {
-            if (rem > 0) zp[0] = o.x;
-            if (rem > 1) zp[1] = o.y;
-            if (rem > 2) zp[2] = o.z;
-            if (rem > 3) zp[3] = o.w;
-        }
-    }
+    float4 v[R][NPX];
+    walk_rows<R>(
+        r0 + ty, r1, ty_n,
+        [&](int e, long p) {
+            if (PF) {
+                const long po = (long)((unsigned)p / HWo) * pstride;
+                m[PF ? e : 0] = ld4_clamp(mean + po, q, C);
+                sc[PF ? e : 0] = ld4_clamp(scale + po, q, C);
+            }
+            if (POOL) {
+                const unsigned up = (unsigned)p, t = up / (unsigned)Wo;
+                const int wo = (int)(up - t * (unsigned)Wo);
+                const unsigned n = t / (unsigned)Ho;
+                const int ho = (int)(t - n * (unsigned)Ho);
+                const float* yb = y + (((long)n * H + 2 * ho) * W + 2 * wo) * ld_y + q * 4;
+#pragma unroll
+                for (int k = 0; k < NPX; ++k) v[e][k] = ld4_window(yb, W, ld_y, k >> 1, k & 1);
+            } else {
+                v[e][0] = *reinterpret_cast<const float4*>(y + p * ld_y + q * 4);
+            }
+        },
+        [&](int e, long p) {
+            const float4 mk = m[PF ? e : 0], sk = sc[PF ? e : 0];
+            float4 o;
+            if (POOL)
+                o = bn_apply4_pool([&](int dy, int dx) { return v[e][POOL ? dy * 2 + dx : 0]; }, mk, sk, be, slope);
+            else
+                o = bn_apply4(v[e][0], mk, sk, be, slope);
+            store_quad<ST>(z + p * ld_z + z_off + q * 4, o, rem);
+        },
+        [&]() {
+            if (!PF) MNK_USED_AFTER_LOADS(m[0]);      // (v - m is the first thing done with a loaded value)
+        });
+}
+
+// rows in flight of bn_act_bwd_apply_kernel, as many as 128 registers (four blocks per CU) hold: four; three where a row is more
+// loads or more index arithmetic (pooled with an addend; dz lane by lane when pooled or with an addend); per-frame statistics carry
+// five constant quads with every row: two rows, one when pooled or with dz lane by lane
+constexpr int bwd_apply_rows(bool POOL, bool DZV, bool PF, bool ADD) {
+    return PF ? ((POOL || !DZV) ? 1 : 2) : ((POOL && ADD) || (!DZV && (POOL || ADD))) ? 3 : ROWS_IN_FLIGHT;
 }
 
 // sums = [sum g][sum g*xhat], each frames*C long when the statistics are per frame (L.pstride = C)
+// POOL, DZV: BwdLoader::fetch's cases; PF: per-frame statistics (the constants of a row are loaded with the row, unconditionally);
+// ADD: with an addend
+template <bool POOL, bool DZV, bool PF, bool ADD>
 __global__ void __launch_bounds__(256) bn_act_bwd_apply_kernel(BwdLoader L, const float* __restrict__ sums,
                                                                double count, int training, int FC,
                                                                float* __restrict__ dy, int ld_dy, long rows, int C,
                                                                int nv, int tx_n, int ty_n, long rows_per_block,
                                                                float* __restrict__ dy_partial,
-                                                               const float* __restrict__ addend, int ld_add) {
+                                                               const float* addend, int ld_add) {
     // dy_partial (optional): [gridDim.y][2][4 * nv] with the column sums of the written dy in slot 0 -- the bias
     // gradient of the convolution in front of this norm layer (Conv3x3Fn.backward), saving its pass over dy
     // addend (optional): a second gradient of the same tensor, added here -- the skip path of a residual block whose
@@ -583,31 +785,52 @@ __global__ void __launch_bounds__(256) bn_act_bwd_apply_kernel(BwdLoader L, cons
     long r1 = r0 + rows_per_block;
     if (r1 > rows) r1 = rows;
     const float inv = training ? (float)(1.0 / count) : 0.f;
-    long cur = -1;
-    float4 sc = make_float4(0.f, 0.f, 0.f, 0.f), k1 = sc, k2 = sc;
-    BwdLoader::State st;
-    L.init(st);
-#pragma unroll 2
-    for (long r = r0 + ty; r < r1; r += ty_n) {
-        const long po = L.poff(r);
-        if (po != cur) {            // (re)load the per-channel constants: once for BatchNorm, once per frame otherwise
-            cur = po;
-            sc = ld4_guard(L.scale + po, q, C);
-            if (training) {
-                k1 = ld4_guard(sums + po, q, C);
-                k2 = ld4_guard(sums + FC + po, q, C);
-                k1 = f4_scale(k1, inv);
-                k2 = f4_scale(k2, inv);
-            }
-        }
-        float4 g, xh;
-        L.load(r, q, st, g, xh);
-        float4 o = bn_dx4(g, xh, sc, k1, k2);
-        if (addend) o = f4_add(o, *reinterpret_cast<const float4*>(addend + r * ld_add + q * 4));
-        zero_pad_lanes(o, C - q * 4);       // keep pad channels of dy at zero
-        *reinterpret_cast<float4*>(dy + r * ld_dy + q * 4) = o;
-        csum = f4_add(csum, o);
+    // evaluation mode has no sums: the two means are zero; their (unconditional) loads then read the scale vector and are dropped
+    const float* ksrc = training ? sums : L.scale;
+    const int koff = training ? FC : 0;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    constexpr int R = bwd_apply_rows(POOL, DZV, PF, ADD), NK = PF ? R : 1, NA = ADD ? R : 1;
+    BwdConsts kc[NK];
+    float4 k1[NK], k2[NK];
+    auto load_consts = [&](int i, long po) {
+        L.consts(po, q, kc[i]);
+        k1[i] = ld4_clamp(ksrc + po, q, C);
+        k2[i] = ld4_clamp(ksrc + koff + po, q, C);
+    };
+    auto scale_means = [&](int i) {
+        k1[i] = training ? f4_scale(k1[i], inv) : zero;
+        k2[i] = training ? f4_scale(k2[i], inv) : zero;
+    };
+    if (!PF) {
+        load_consts(0, 0);
+        scale_means(0);
     }
+    BwdRaw w[R];
+    float4 add[NA];
+    walk_rows<R>(
+        r0 + ty, r1, ty_n,
+        [&](int e, long r) {
+            if (PF) load_consts(PF ? e : 0, L.poff(r));
+            L.fetch<POOL, DZV>(r, q, w[e]);
+            if (ADD) add[ADD ? e : 0] = *reinterpret_cast<const float4*>(addend + r * ld_add + q * 4);
+        },
+        [&](int e, long r) {
+            const int i = PF ? e : 0;
+            if (PF) scale_means(i);
+            float4 g, xh;
+            L.finish(w[e], kc[i], q, g, xh);
+            float4 o = bn_dx4(g, xh, kc[i].sc, k1[i], k2[i]);
+            if (ADD) o = f4_add_exact(o, add[ADD ? e : 0]);
+            zero_pad_lanes(o, C - q * 4);       // keep pad channels of dy at zero
+            *reinterpret_cast<float4*>(dy + r * ld_dy + q * 4) = o;
+            csum = f4_add(csum, o);
+        },
+        [&]() {
+            if (!PF) {
+                L.issued<POOL, R>(kc[0], w);
+                MNK_USED_AFTER_LOADS(k1[0]);
+            }
+        });
     }
     if (dy_partial) {
         red[threadIdx.x] = csum;
@@ -986,6 +1209,91 @@ static void launch_partials(const Loader& L, const Map2D& m, long rows, int fram
                        ld, m.tx, m.ty, m.rows_per_block, ws);
 }
 
+// the block-uniform cases of the row loops are chosen here, once per launch: the kernels have no such branch
+static inline bool dz_is_quads(const BwdLoader& L) { return ((L.ld_dz | L.dz_off) & 3) == 0; }
+
+static void launch_bwd_partials(const BwdLoader& L, const Map2D& m, long rows, int frames, int ld, float* ws, hipStream_t s) {
+    const bool dzv = dz_is_quads(L);
+    if (L.pool) {
+        if (dzv) launch_partials(BwdRows<true, true>{L}, m, rows, frames, ld, ws, s);
+        else launch_partials(BwdRows<true, false>{L}, m, rows, frames, ld, ws, s);
+    } else {
+        if (dzv) launch_partials(BwdRows<false, true>{L}, m, rows, frames, ld, ws, s);
+        else launch_partials(BwdRows<false, false>{L}, m, rows, frames, ld, ws, s);
+    }
+}
+
+struct BwdApplyLaunch {
+    BwdLoader L;
+    const float* sums;
+    double count;
+    int training, FC;
+    float* dy;
+    int ld_dy;
+    long rows;
+    int C;
+    float* dy_partial;
+    const float* addend;      // (only with BatchNorm statistics: L.pstride == 0)
+    int ld_add;
+};
+template <bool POOL, bool DZV, bool PF, bool ADD>
+static void launch_bwd_apply_as(const BwdApplyLaunch& a, const Map2D& m, hipStream_t s) {
+    hipLaunchKernelGGL((bn_act_bwd_apply_kernel<POOL, DZV, PF, ADD>), dim3(m.col_tiles, m.row_blocks), dim3(256), 0, s, a.L, a.sums,
+                       a.count, a.training, a.FC, a.dy, a.ld_dy, a.rows, a.C, round_up(a.C, 4) / 4, m.tx, m.ty, m.rows_per_block,
+                       a.dy_partial, a.addend, a.ld_add);
+}
+template <bool POOL, bool DZV>
+static void launch_bwd_apply_pd(const BwdApplyLaunch& a, const Map2D& m, hipStream_t s) {
+    if (a.addend) launch_bwd_apply_as<POOL, DZV, false, true>(a, m, s);
+    else if (a.L.pstride) launch_bwd_apply_as<POOL, DZV, true, false>(a, m, s);
+    else launch_bwd_apply_as<POOL, DZV, false, false>(a, m, s);
+}
+static void launch_bwd_apply(const BwdApplyLaunch& a, const Map2D& m, hipStream_t s) {
+    const bool dzv = dz_is_quads(a.L);
+    if (a.L.pool) {
+        if (dzv) launch_bwd_apply_pd<true, true>(a, m, s);
+        else launch_bwd_apply_pd<true, false>(a, m, s);
+    } else {
+        if (dzv) launch_bwd_apply_pd<false, true>(a, m, s);
+        else launch_bwd_apply_pd<false, false>(a, m, s);
+    }
+}
+
+struct FwdApplyLaunch {
+    const float *y, *mean, *scale, *beta;
+    int ld_y, pstride;
+    float* z;
+    int ld_z, z_off, N, H, W, C;
+    float slope;
+    bool pool, finalize;
+    FwdFinalize fin;
+};
+template <int POOL, bool FIN, bool PF, int ST>
+static void launch_fwd_apply_as(const FwdApplyLaunch& a, const Map2D& m, hipStream_t s) {
+    hipLaunchKernelGGL((bn_act_fwd_kernel<POOL, FIN, PF, ST>), dim3(m.col_tiles, m.row_blocks), dim3(256), 0, s, a.y, a.ld_y, a.mean,
+                       a.scale, a.beta, a.pstride, a.z, a.ld_z, a.z_off, a.N, a.H, a.W, a.C, a.slope, m.tx, m.ty, m.rows_per_block,
+                       a.fin);
+}
+template <int POOL, bool FIN, bool PF>
+static void launch_fwd_apply_st(const FwdApplyLaunch& a, const Map2D& m, hipStream_t s) {
+    const int ldc = round_up(a.C, 4);
+    const bool vec_store = ((a.z_off & 3) == 0) && ((a.ld_z & 3) == 0);
+    const bool owns_pads = a.z_off == 0 && a.ld_z == ldc;   // z is a plain act: its pad channels are written (as zero) here
+    if (!vec_store) launch_fwd_apply_as<POOL, FIN, PF, 0>(a, m, s);
+    else if (owns_pads || ldc == a.C) launch_fwd_apply_as<POOL, FIN, PF, 1>(a, m, s);
+    else launch_fwd_apply_as<POOL, FIN, PF, 2>(a, m, s);
+}
+template <int POOL>
+static void launch_fwd_apply_p(const FwdApplyLaunch& a, const Map2D& m, hipStream_t s) {
+    if (a.finalize) launch_fwd_apply_st<POOL, true, false>(a, m, s);      // (finished sums: BatchNorm statistics only)
+    else if (a.pstride) launch_fwd_apply_st<POOL, false, true>(a, m, s);
+    else launch_fwd_apply_st<POOL, false, false>(a, m, s);
+}
+static void launch_fwd_apply(const FwdApplyLaunch& a, const Map2D& m, hipStream_t s) {
+    if (a.pool) launch_fwd_apply_p<1>(a, m, s);
+    else launch_fwd_apply_p<0>(a, m, s);
+}
+
 static inline int grid_for(long total, int cap = 2048) {
     long b = (total + 255) / 256;
     if (b < 1) b = 1;
@@ -1096,14 +1404,9 @@ int mnk_norm_act_fwd(const float* y, int ld_y, const float* mean, const float* s
     MNK_REQUIRE((long)N * H * W < (1L << 31));
     ProfScope prof(K_BN_APPLY, s, (double)N * H * W * C * 4 * (pool ? 1.25 : 2.0));
     const int pstride = per_frame ? C : 0;
-    Map2D m = make_map(rows, round_up(C, 4), 2, 2048);     // no reduction here: small layers want blocks, not rows per thread
-    const dim3 grid(m.col_tiles, m.row_blocks);
-    if (pool)
-        hipLaunchKernelGGL(bn_act_fwd_kernel<1>, grid, dim3(256), 0, s, y, ld_y, mean, scale, beta, pstride, z, ld_z, z_off,
-                           N, H, W, C, slope, m.tx, m.ty, m.rows_per_block, FwdFinalize());
-    else
-        hipLaunchKernelGGL(bn_act_fwd_kernel<0>, grid, dim3(256), 0, s, y, ld_y, mean, scale, beta, pstride, z, ld_z, z_off,
-                           N, H, W, C, slope, m.tx, m.ty, m.rows_per_block, FwdFinalize());
+    Map2D m = make_map(rows, round_up(C, 4), g_bn_fwd_rpt, g_bn_fwd_blocks);
+    launch_fwd_apply(FwdApplyLaunch{y, mean, scale, beta, ld_y, pstride, z, ld_z, z_off, N, H, W, C, slope, pool != 0, false,
+                                    FwdFinalize()}, m, s);
     MNK_LAUNCH_CHECK();
     return MNK_OK;
 }
@@ -1124,7 +1427,7 @@ int mnk_norm_act_bwd_stats(const float* y, int ld_y, const float* dz, int ld_dz,
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(K_BN_BWD, s, (double)N * H * W * C * 4 * (pool ? 1.25 : 2.0));
     BwdLoader L{y, dz, mean, invstd, scale, beta, ld_y, ld_dz, dz_off, H, W, C, pool, per_frame ? C : 0, slope};
-    launch_partials(L, m, rows, frames, ldc, ws, s);
+    launch_bwd_partials(L, m, rows, frames, ldc, ws, s);
     hipLaunchKernelGGL(colsum2_final_kernel, dim3(ceil_div(2 * frames * C, 4)), dim3(256), 0, s, ws, m.row_blocks, ldc, C, frames,
                        sums, 2);
     MNK_LAUNCH_CHECK();
@@ -1146,9 +1449,7 @@ int mnk_norm_act_bwd_apply(const float* y, int ld_y, const float* dz, int ld_dz,
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(K_BN_BWD, s, (double)rows * C * 4 * (pool ? 2.25 : 3.0));
     BwdLoader L{y, dz, mean, invstd, scale, beta, ld_y, ld_dz, dz_off, H, W, C, pool, per_frame ? C : 0, slope};
-    hipLaunchKernelGGL(bn_act_bwd_apply_kernel, dim3(m.col_tiles, m.row_blocks), dim3(256), 0, s, L, sums, count, training,
-                       (per_frame ? N : 1) * C, dy, ld_dy, rows, C, ldc / 4, m.tx, m.ty, m.rows_per_block, (float*)nullptr,
-                       (const float*)nullptr, 0);
+    launch_bwd_apply(BwdApplyLaunch{L, sums, count, training, (per_frame ? N : 1) * C, dy, ld_dy, rows, C, nullptr, nullptr, 0}, m, s);
     MNK_LAUNCH_CHECK();
     return MNK_OK;
 }
@@ -1174,8 +1475,7 @@ int mnk_bn_act_bwd_apply_add_colsum(const float* y, int ld_y, const float* dz, i
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(K_BN_BWD, s, (double)rows * C * 4 * (pool ? 2.25 : 3.0));
     BwdLoader L{y, dz, mean, invstd, scale, beta, ld_y, ld_dz, dz_off, H, W, C, pool, 0, relu ? 0.f : -1.f};
-    hipLaunchKernelGGL(bn_act_bwd_apply_kernel, dim3(m.col_tiles, m.row_blocks), dim3(256), 0, s, L, sums, count, training,
-                       C, dy, ld_dy, rows, C, ldc / 4, m.tx, m.ty, m.rows_per_block, ws, addend, ld_add);
+    launch_bwd_apply(BwdApplyLaunch{L, sums, count, training, C, dy, ld_dy, rows, C, ws, addend, ld_add}, m, s);
     hipLaunchKernelGGL(colsum2_final_kernel, dim3(ceil_div(C, 4)), dim3(256), 0, s, ws, m.row_blocks, ldc, C, 1, dy_sums, 1);
     MNK_LAUNCH_CHECK();
     return MNK_OK;
@@ -1270,7 +1570,7 @@ int mnk_bn_act_bwd_stats_sync(void* p2p, const float* y, int ld_y, const float* 
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(K_BN_BWD, s, (double)N * H * W * C * 4 * (pool ? 1.25 : 2.0));
     BwdLoader L{y, dz, mean, invstd, scale, beta, ld_y, ld_dz, dz_off, H, W, C, pool, 0, relu ? 0.f : -1.f};
-    launch_partials(L, m, rows, 1, ldc, ws, s);
+    launch_bwd_partials(L, m, rows, 1, ldc, ws, s);
     rc = launch_final_sync(__func__, p2p, ws, m.row_blocks, ldc, C, sums_local, sums_global, timeout_ms, s);
     if (rc != MNK_OK) return rc;
     MNK_LAUNCH_CHECK();
@@ -1296,16 +1596,10 @@ int mnk_bn_act_fwd_sums(const float* y, int ld_y, const float* sums, double coun
     hipStream_t s = (hipStream_t)stream;
     const long rows = (long)N * (pool ? H / 2 : H) * (pool ? W / 2 : W);
     ProfScope prof(K_BN_APPLY, s, (double)N * H * W * C * 4 * (pool ? 1.25 : 2.0));
-    Map2D m = make_map(rows, round_up(C, 4), 2, 2048);
-    const dim3 grid(m.col_tiles, m.row_blocks);
+    Map2D m = make_map(rows, round_up(C, 4), g_bn_fwd_rpt, g_bn_fwd_blocks);
     const FwdFinalize fin{sums, gamma, running_mean, running_var, mean, invstd, scale, count, momentum, eps, update_running};
-    const float slope = relu ? 0.f : -1.f;
-    if (pool)
-        hipLaunchKernelGGL((bn_act_fwd_kernel<1, true>), grid, dim3(256), 0, s, y, ld_y, (const float*)nullptr,
-                           (const float*)nullptr, beta, 0, z, ld_z, z_off, N, H, W, C, slope, m.tx, m.ty, m.rows_per_block, fin);
-    else
-        hipLaunchKernelGGL((bn_act_fwd_kernel<0, true>), grid, dim3(256), 0, s, y, ld_y, (const float*)nullptr,
-                           (const float*)nullptr, beta, 0, z, ld_z, z_off, N, H, W, C, slope, m.tx, m.ty, m.rows_per_block, fin);
+    launch_fwd_apply(FwdApplyLaunch{y, nullptr, nullptr, beta, ld_y, 0, z, ld_z, z_off, N, H, W, C, relu ? 0.f : -1.f, pool != 0,
+                                    true, fin}, m, s);
     MNK_LAUNCH_CHECK();
     return MNK_OK;
 }
