@@ -920,7 +920,7 @@ def _bind_bn(z, rec):
     key = id(z)
     _BN_OF[key] = (weakref.ref(z, lambda _r, key=key: _BN_OF.pop(key, None)), rec)
 _LAST_BN = [None]                         # BNActFn.forward -> bn_act(): the record of the launch that just ran
-_DZ_STATS = {}                            # dx.data_ptr() -> (dx, partials, rows, y.data_ptr()); dx is held, so the key is unique
+_DZ_STATS = {}                            # dx.data_ptr() -> (dx, partials, rows, y.data_ptr(), dx._version); dx is held: a unique key
 DZ_STATS_COUNT = [0, 0]                   # norm-layer backward passes that took the hand-over / that made their own pass (tests)
 
 
@@ -956,6 +956,40 @@ def handover_state():
     return {k: v for k, v in slots.items() if v}
 
 
+# ---- what the running backward pass asked for ---------------------------------------------------------------------------------------
+# `ctx.needs_input_grad[i]` of a custom Function says that input i REQUIRES a gradient, not that this pass delivers one:
+# torch.autograd.grad(loss, x) and loss.backward(inputs=[x]) run the node with the flag of every parameter still True.  A returned
+# gradient nobody asked for is dropped by the engine, but a SIDE EFFECT of computing it -- weight-gradient partials written towards
+# an optimiser's sink (DeferredReducer.wgrad) -- stays and is summed into the next step.  The engine knows: inside a backward pass
+# torch._C._will_engine_execute_node(node) answers for the node behind input i (a parameter's AccumulateGrad).
+_WILL_EXECUTE = getattr(torch._C, "_will_engine_execute_node", None)
+GRAD_DELIVERED, GRAD_RETURNED, GRAD_UNWANTED = "delivered", "returned", "unwanted"
+
+
+def edge_index(args, i):
+    """the position of forward argument `i` among the node's edges (`ctx.next_functions`): only tensor arguments have one"""
+    return sum(1 for a in args[:i] if torch.is_tensor(a))
+
+
+def param_grad_request(ctx, edge):
+    """What the running backward pass does with the gradient of the parameter behind edge `edge` (edge_index) of the node `ctx`:
+    GRAD_DELIVERED  it reaches the parameter (backward(), backward(inputs=[... p ...])): side effects towards a sink are in order;
+    GRAD_RETURNED   the parameter itself is an input of torch.autograd.grad(): the caller gets the tensor this node returns and
+                    p.grad stays as it is -- the gradient is computed by the per-layer path, nothing is written towards a sink;
+    GRAD_UNWANTED   nobody asked (autograd.grad(loss, x), backward(inputs=[x])): no weight / bias gradient work at all.
+    A torch without the query keeps GRAD_DELIVERED (the behaviour before the query was used)."""
+    if _WILL_EXECUTE is None:
+        return GRAD_DELIVERED
+    node = ctx.next_functions[edge][0]
+    if node is None:
+        return GRAD_DELIVERED
+    try:
+        return GRAD_DELIVERED if _WILL_EXECUTE(node) else GRAD_UNWANTED
+    except RuntimeError:
+        # "A leaf node was passed to _will_engine_execute_node but we are currently running autograd.grad()"
+        return GRAD_RETURNED
+
+
 class Conv3x3Fn(_Fn):
     """nn.Conv3d((1,3,3), padding (0,1,1)) over the channel concatenation [x0 | x1], optionally read through the
     nearest x2 up-sampling (UpBlock3D, modules/util.py:83-85), plus bias and residual add (ResBlock3D :66-67)."""
@@ -980,6 +1014,7 @@ class Conv3x3Fn(_Fn):
             need = [bool(cc and ctx.needs_input_grad[i]) for i, cc in enumerate((c0, c1))]
             e = _pack_entry(weight, cout, c0, c1, need, up, dead1x1=up and up1x1_dead_taps(n, hs, ws_))
             wp, ctx.wd = e.wp, list(e.wd)
+            ctx.edges = (edge_index((x0, x1, weight), 2), edge_index((x0, x1, weight, bias), 3))      # of weight and bias
         else:
             wp = _packed_fwd_weight(weight, cout, c0, c1, up)
         y, sums = _conv_launch(x0, c0, x1, c1, ups, wp, bias, residual, n, h, w, cout, want_stats, up, eval_defer, ctx.bf16)
@@ -1038,17 +1073,19 @@ class Conv3x3Fn(_Fn):
                 rec = None
             dx, st = _gemm_launch(form, dy, cout, None, 0, wp, None, res, n, hd, wd, cc, 2 | (16 if ctx.bf16 else 0), bn=rec)
             if rec is not None and st is not None:
-                _DZ_STATS[dx.data_ptr()] = (dx, st, st.numel() // (2 * dx.shape[-1]), rec.y.data_ptr())
+                _DZ_STATS[dx.data_ptr()] = (dx, st, st.numel() // (2 * dx.shape[-1]), rec.y.data_ptr(), dx._version)
             if ups and not ctx.up:
                 dxs = torch.empty(n, h // 2, w // 2, ceil4(cc), dtype=torch.float32, device=dy.device)
                 _call("mnk_sumpool2x2", dy, _p(dx), dx.shape[-1], _p(dxs), dxs.shape[-1], n, h, w, cc)
                 dx = dxs
             grads[i] = dx
         dw = None
-        if ctx.needs_input_grad[2]:
+        want_w = param_grad_request(ctx, ctx.edges[0]) if ctx.needs_input_grad[2] else GRAD_UNWANTED
+        if want_w != GRAD_UNWANTED:
             # an optimiser of mnk.optim owns this parameter: the GEMM writes (the partials of) its gradient towards the
             # optimiser's flat buffer and the split reduction waits for the one launch that serves every layer
-            owner = wgrad_sink_owner(weight)
+            # (GRAD_RETURNED: the caller of torch.autograd.grad gets dW itself, the sink is left alone)
+            owner = wgrad_sink_owner(weight) if want_w == GRAD_DELIVERED else None
             taken = [False, False]
             # | 2: MNK_CONV_CLEAN_PADS (x and dy are acts of this module); | 8: MNK_WGRAD_BF16, the precision the forward recorded
             wflags = int(ups) | 2 | (8 if ctx.bf16 else 0)
@@ -1071,8 +1108,10 @@ class Conv3x3Fn(_Fn):
                 owner.add_to_sink(weight, dw)        # a further contribution before the step (slow path)
                 dw = None
         db = None
-        if has_bias and ctx.needs_input_grad[3]:
-            slot, _DY_SUMS[0] = _DY_SUMS[0], None
+        # the slot is one-shot: whatever the norm layer behind this convolution left is taken here, bias or no bias (a frozen or
+        # absent bias would otherwise leave a dy-sized tensor pinned until the next norm layer's backward)
+        slot, _DY_SUMS[0] = _DY_SUMS[0], None
+        if has_bias and ctx.needs_input_grad[3] and param_grad_request(ctx, ctx.edges[1]) != GRAD_UNWANTED:
             if slot is not None and slot[0] is dy_in and slot[1] is None:
                 db = None                      # a training-mode BatchNorm follows: the bias gradient is exactly zero
             elif slot is not None and slot[0] is dy_in and slot[1].numel() == cout:
@@ -1438,8 +1477,9 @@ class BNActFn(_Fn):
         sums = torch.empty(2 * c, dtype=torch.float32, device=y.device)
         pre = _DZ_STATS.pop(dz.data_ptr(), None)
         local = torch.empty(2 * c, dtype=torch.float32, device=y.device) if sync is not None else sums
-        if pre is not None and pre[0].shape == dz.shape and pre[3] == y.data_ptr() and not pool:
+        if pre is not None and pre[0].shape == dz.shape and pre[3] == y.data_ptr() and not pool and pre[0]._version == pre[4]:
             # this gradient is the data-gradient GEMM's own output: its epilogue left the statistics' first stage
+            # (the version: an in-place gradient hook -- z.register_hook(lambda g: g.mul_(2)) -- keeps the address and changes dz)
             if sync is not None:
                 _call("mnk_bn_stats_finish_sync", y, sync, _p(pre[1]), pre[2], ld, c, _p(local), _p(sums), mdist.P2P_TIMEOUT_MS)
             else:
@@ -1606,8 +1646,9 @@ class ConvKxKFn(_Fn):
                 wp = SCRATCH.get("pack", _query(_FORMS["kxk"].packed, cin, cout, 0, nt), dy)
                 _call("mnk_conv2d_pack_dgrad", dy, _p(weight), _p(wp), cout, cin, 0, cin, nt)
             dx, _ = _gemm_launch("kxk", dy, cout, None, 0, wp, None, None, n, hi, wi, cin, 2, kxk=(ho, wo, kh, kw, kh - 1 - pad))
-        if ctx.needs_input_grad[1] and not _SKIP_PARAM_GRADS[0]:
-            owner = wgrad_sink_owner(weight)
+        want_w = param_grad_request(ctx, 1) if ctx.needs_input_grad[1] and not _SKIP_PARAM_GRADS[0] else GRAD_UNWANTED      # (edges: x, weight, bias)
+        if want_w != GRAD_UNWANTED:
+            owner = wgrad_sink_owner(weight) if want_w == GRAD_DELIVERED else None      # (GRAD_RETURNED: see Conv3x3Fn._backward)
             if owner is None or not owner.reducer.wgrad(weight, x, x.shape[-1], cin, 0, hi, wi, kh, kw, pad, dy,
                                                         dy.shape[-1], cout, cin, 0, n, ho, wo):
                 dw = torch.empty_like(weight)
@@ -1618,7 +1659,7 @@ class ConvKxKFn(_Fn):
                 if owner is not None:
                     owner.add_to_sink(weight, dw)
                     dw = None
-        if has_bias and ctx.needs_input_grad[2] and not _SKIP_PARAM_GRADS[0]:
+        if has_bias and ctx.needs_input_grad[2] and not _SKIP_PARAM_GRADS[0] and param_grad_request(ctx, 2) != GRAD_UNWANTED:
             db = channel_sums(dy, cout)[:cout]
         return dx, dw, db, None, None, None, None, None
 

@@ -393,7 +393,9 @@ class MnkAdam(torch.optim.Optimizer, FlatGrads):
     """torch.optim.Adam(params, lr, betas, eps) semantics (no amsgrad / weight decay), one kernel launch per step."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
-        super(MnkAdam, self).__init__(params, dict(lr=lr, betas=betas, eps=eps))
+        # (weight_decay / amsgrad: the values this optimiser implements, spelled out so that its state_dict() loads into a
+        # torch.optim.Adam, whose step reads them from the loaded group -- tests/test_optimizer_contract.py)
+        super(MnkAdam, self).__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=0, amsgrad=False))
         if len(self.param_groups) != 1:
             raise ValueError("MnkAdam takes one parameter group (train.py:81-83 builds one optimiser per network)")
         self._init_sinks(self.param_groups[0]["params"])
