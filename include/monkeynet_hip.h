@@ -679,6 +679,21 @@ int mnk_kp_hull_area(const float* points, int K, float* area, void* stream);
 int mnk_kp_normalize(const float* mean_v, const float* var_v, const float* mean_a, const float* var_a, int B, int D, int K,
                      const float* area_a, const float* area_v, int move_location, int clip_mean, int adapt_variance,
                      float* mean_out, float* var_out, void* stream);
+/* The same normalisation for a driving video that arrives in pieces (transfer.py:31-62,65-79 and demo.py:60-71 normalise every
+ * frame against the FIRST frame of the whole video): the first frame's key-points are kept in anchor buffers.
+ * mnk_kp_anchor_update: one block.  *anchored == 0: frame 0 of mean_v [B][D][K][2] / var_v [B][D][K][4] -> anchor_mean [B][K][2]
+ *   / anchor_var [B][K][4] (NULL: means only), with want_area the hull area of mean_v[0, 0] (K in 3..32; batch entry 0 only, the
+ *   reference's own quirk) -> *anchor_area, then *anchored = 1.  *anchored != 0: writes nothing.  The flag is device memory: the
+ *   push that anchors and every later one issue the same launches (one captured program).
+ * mnk_kp_normalize_anchored: mnk_kp_normalize with the first frame read from anchor_mean / anchor_var and area_v from
+ *   *anchor_area -- the same kernel with another first-frame pointer and stride, so a video normalised piece by piece equals the
+ *   whole video's mnk_kp_normalize bit for bit.  adapt_variance needs anchor_var. */
+int mnk_kp_anchor_update(const float* mean_v, const float* var_v, int B, int D, int K, int want_area, float* anchor_mean,
+                         float* anchor_var, float* anchor_area, int* anchored, void* stream);
+int mnk_kp_normalize_anchored(const float* mean_v, const float* var_v, const float* anchor_mean, const float* anchor_var,
+                              const float* mean_a, const float* var_a, int B, int D, int K, const float* area_a,
+                              const float* anchor_area, int move_location, int clip_mean, int adapt_variance, float* mean_out,
+                              float* var_out, void* stream);
 
 /* ---- key-point -> movement embedding (modules/movement_embedding.py:42-92, keypoint_detector.py:7-40) ----
  * one kernel renders, per slot (background first when add_bg): [heat-map (driving - source when

@@ -830,8 +830,8 @@ __global__ void __launch_bounds__(256) kp_clip_var_bwd_kernel(const float* __res
 // ---- transfer-time key-point normalisation (transfer.py:31-62 normalize_kp) on the device --------------------------------
 // area of the convex hull of K <= 32 points (scipy.spatial.ConvexHull(points).volume in 2-D): Andrew's monotone chain and
 // the shoelace formula, one thread (transfer.py:34-36 uses the hulls of the first frame's key-points only)
-__global__ void kp_hull_area_kernel(const float* __restrict__ pts, int K, float* __restrict__ area) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+// (one body, not inlined: kp_hull_area_kernel and kp_anchor_update_kernel run the same instructions)
+__device__ __attribute__((noinline)) float kp_hull_area(const float* __restrict__ pts, int K) {
     float x[32], y[32];
     for (int i = 0; i < K; ++i) {
         x[i] = pts[2 * i];
@@ -866,15 +866,54 @@ __global__ void kp_hull_area_kernel(const float* __restrict__ pts, int K, float*
         const int p = hull[i], q = hull[(i + 1) % n];
         a2 += x[p] * y[q] - x[q] * y[p];
     }
-    *area = 0.5f * fabsf(a2);
+    return 0.5f * fabsf(a2);
+}
+
+__global__ void kp_hull_area_kernel(const float* __restrict__ pts, int K, float* __restrict__ area) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    *area = kp_hull_area(pts, K);
+}
+
+// the anchor of an animation session (transfer.py:65-79 / demo.py:60-71 normalise every frame of a driving video against its
+// FIRST frame; a video that arrives in pieces keeps that frame's key-points here): one block.  *anchored == 0: frame 0 of
+// mean_v [B][D][K][2] / var_v [B][D][K][4] -> anchor_mean [B][K][2] / anchor_var [B][K][4], the hull area of [0, 0] -> *anchor_area
+// (want_area; the reference's quirk: batch entry 0 only), then *anchored = 1 behind a barrier.  *anchored != 0: nothing is written.
+// The flag is device memory, so the launch list of the push that anchors and of every later push is the same (one hipGraph).
+__global__ void __launch_bounds__(256) kp_anchor_update_kernel(const float* __restrict__ mean_v, const float* __restrict__ var_v,
+                                                               int B, int D, int K, int want_area,
+                                                               float* __restrict__ anchor_mean, float* __restrict__ anchor_var,
+                                                               float* __restrict__ anchor_area, int* __restrict__ anchored) {
+    if (blockIdx.x != 0) return;
+    const int was = *anchored;             // every thread reads it before the barrier, thread 0 writes it after
+    if (was != 0) return;
+    for (int j = threadIdx.x; j < B * K; j += blockDim.x) {
+        const int b = j / K, k = j - b * K;
+        const long first = ((long)b * D) * K + k;
+        anchor_mean[2 * j] = mean_v[2 * first];
+        anchor_mean[2 * j + 1] = mean_v[2 * first + 1];
+        if (anchor_var) {
+            anchor_var[4 * j] = var_v[4 * first];
+            anchor_var[4 * j + 1] = var_v[4 * first + 1];
+            anchor_var[4 * j + 2] = var_v[4 * first + 2];
+            anchor_var[4 * j + 3] = var_v[4 * first + 3];
+        }
+    }
+    if (want_area && threadIdx.x == 0) *anchor_area = kp_hull_area(mean_v, K);
+    __syncthreads();
+    if (threadIdx.x == 0) *anchored = 1;
 }
 
 // one thread per (batch entry b, driving frame f, key-point k):
 //   mean' = (mean_v[b,f,k] - mean_v[b,0,k]) * sqrt(area_a / area_v) + mean_a[b,0,k]      (move_location; then clamp to [-1,1])
 //   var'  = sym_posdef( var_v[b,f,k] * inverse(var_v[b,0,k]) * var_a[b,0,k] )            (adapt_variance)
+// the first frame [b,0,k] is read at mean_f / var_f + (b * first_stride + k) * (2 | 4): mnk_kp_normalize passes the video itself
+// with first_stride = D * K, mnk_kp_normalize_anchored the anchor buffers [B][K][.] with first_stride = K -- one kernel, one
+// instruction sequence for both
 // sym_posdef = make_symetric_matrix (transfer.py:17-28): (A + A^T) / 2 with eigenvalues <= 0 replaced by 1e-6 (closed form
 // for 2x2: the matrix itself when both eigenvalues are positive)
 __global__ void __launch_bounds__(256) kp_normalize_kernel(const float* __restrict__ mean_v, const float* __restrict__ var_v,
+                                                           const float* __restrict__ mean_f, const float* __restrict__ var_f,
+                                                           long first_stride,
                                                            const float* __restrict__ mean_a, const float* __restrict__ var_a,
                                                            int B, int D, int K, const float* __restrict__ area_a,
                                                            const float* __restrict__ area_v, int move_location, int clip_mean,
@@ -884,12 +923,12 @@ __global__ void __launch_bounds__(256) kp_normalize_kernel(const float* __restri
     if (i >= (long)B * D * K) return;
     const int k = (int)(i % K);
     const int b = (int)(i / ((long)D * K));
-    const long first = ((long)b * D) * K + k, app = (long)b * K + k;
+    const long first = (long)b * first_stride + k, app = (long)b * K + k;
     float mx = mean_v[2 * i], my = mean_v[2 * i + 1];
     if (move_location) {
         const float mult = (area_a && area_v) ? sqrtf(*area_a) / sqrtf(*area_v) : 1.f;
-        mx = (mx - mean_v[2 * first]) * mult + mean_a[2 * app];
-        my = (my - mean_v[2 * first + 1]) * mult + mean_a[2 * app + 1];
+        mx = (mx - mean_f[2 * first]) * mult + mean_a[2 * app];
+        my = (my - mean_f[2 * first + 1]) * mult + mean_a[2 * app + 1];
     }
     if (clip_mean) {
         mx = fminf(fmaxf(mx, -1.f), 1.f);
@@ -900,7 +939,7 @@ __global__ void __launch_bounds__(256) kp_normalize_kernel(const float* __restri
     if (!var_out) return;
     float v00 = var_v[4 * i], v01 = var_v[4 * i + 1], v10 = var_v[4 * i + 2], v11 = var_v[4 * i + 3];
     if (adapt_variance) {
-        const float f00 = var_v[4 * first], f01 = var_v[4 * first + 1], f10 = var_v[4 * first + 2], f11 = var_v[4 * first + 3];
+        const float f00 = var_f[4 * first], f01 = var_f[4 * first + 1], f10 = var_f[4 * first + 2], f11 = var_f[4 * first + 3];
         const float det = det_2x2(f00, f01, f10, f11);
         const float i00 = f11 / det, i01 = -f01 / det, i10 = -f10 / det, i11 = f00 / det;     // matrix_inverse, eps = 0
         const float t00 = v00 * i00 + v01 * i10, t01 = v00 * i01 + v01 * i11;
@@ -1201,8 +1240,36 @@ int mnk_kp_normalize(const float* mean_v, const float* var_v, const float* mean_
     hipStream_t s = (hipStream_t)stream;
     const long n = (long)B * D * K;
     ProfScope prof(K_KEYPOINT, s, (double)n * 48);
-    hipLaunchKernelGGL(kp_normalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, mean_v, var_v, mean_a, var_a, B, D,
-                       K, area_a, area_v, move_location, clip_mean, adapt_variance, mean_out, var_out);
+    hipLaunchKernelGGL(kp_normalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, mean_v, var_v, mean_v, var_v,
+                       (long)D * K, mean_a, var_a, B, D, K, area_a, area_v, move_location, clip_mean, adapt_variance, mean_out, var_out);
+    MNK_LAUNCH_CHECK();
+    return MNK_OK;
+}
+
+int mnk_kp_anchor_update(const float* mean_v, const float* var_v, int B, int D, int K, int want_area, float* anchor_mean,
+                         float* anchor_var, float* anchor_area, int* anchored, void* stream) {
+    MNK_REQUIRE(mean_v && anchor_mean && anchored && B > 0 && D > 0 && K > 0 && (!anchor_var || var_v));
+    MNK_REQUIRE((long)B * K <= 0x7fffffffl);
+    MNK_REQUIRE(!want_area || (anchor_area && K >= 3 && K <= 32));
+    hipLaunchKernelGGL(kp_anchor_update_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, mean_v, var_v, B, D, K, want_area,
+                       anchor_mean, anchor_var, anchor_area, anchored);
+    MNK_LAUNCH_CHECK();
+    return MNK_OK;
+}
+
+int mnk_kp_normalize_anchored(const float* mean_v, const float* var_v, const float* anchor_mean, const float* anchor_var,
+                              const float* mean_a, const float* var_a, int B, int D, int K, const float* area_a,
+                              const float* anchor_area, int move_location, int clip_mean, int adapt_variance, float* mean_out,
+                              float* var_out, void* stream) {
+    MNK_REQUIRE(mean_v && anchor_mean && mean_a && mean_out && B > 0 && D > 0 && K > 0 && (!var_out || var_v));
+    MNK_REQUIRE(!adapt_variance || (var_v && var_a && var_out && anchor_var));
+    MNK_REQUIRE((area_a == nullptr) == (anchor_area == nullptr));
+    hipStream_t s = (hipStream_t)stream;
+    const long n = (long)B * D * K;
+    ProfScope prof(K_KEYPOINT, s, (double)n * 48);
+    hipLaunchKernelGGL(kp_normalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, mean_v, var_v, anchor_mean, anchor_var,
+                       (long)K, mean_a, var_a, B, D, K, area_a, anchor_area, move_location, clip_mean, adapt_variance, mean_out,
+                       var_out);
     MNK_LAUNCH_CHECK();
     return MNK_OK;
 }

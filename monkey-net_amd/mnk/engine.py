@@ -612,11 +612,15 @@ class Reconstructor:
         return self._static_out
 
 
-def normalize_kp(kp_video, kp_appearance, movement_mult=False, move_location=False, adapt_variance=False, clip_mean=False):
+def normalize_kp(kp_video, kp_appearance, movement_mult=False, move_location=False, adapt_variance=False, clip_mean=False,
+                 anchor=None):
     """transfer.py:31-62 on the device, same arguments and return value (a new key-point dict): the convex-hull areas
     (transfer.py:34-36; the reference copies the key-points to the host for scipy), the re-centring on the source's
     key-points and the covariance transfer with its symmetric positive-definite repair are two kernel launches, no
-    host synchronisation."""
+    host synchronisation.
+    anchor: a mnk.animation.KpAnchor -- `kp_video` is a piece of a longer video: its "first frame" is the first frame seen since
+    the anchor was reset (this call's frame 0 when the anchor is clear), so consecutive pieces give what one call on the whole
+    video gives, bit for bit (mnk_kp_anchor_update + mnk_kp_normalize_anchored)."""
     mean_v = kp_video['mean'].contiguous().float()
     mops._check_device(mean_v)
     b, d, k, _ = mean_v.shape
@@ -629,6 +633,9 @@ def normalize_kp(kp_video, kp_appearance, movement_mult=False, move_location=Fal
         raise NameError("clip_mean without move_location is an error in the reference too (transfer.py:49)")
     if not (move_location or adapt):
         return {key: v for key, v in kp_video.items()}
+    if anchor is not None:
+        return _normalize_kp_anchored(kp_video, mean_v, var_v, mean_a, var_a, bool(movement_mult), bool(move_location), bool(clip_mean),
+                                      adapt, anchor)
     area_a = area_v = None
     if movement_mult:
         area_a = torch.empty(1, dtype=torch.float32, device=mean_v.device)
@@ -647,6 +654,31 @@ def normalize_kp(kp_video, kp_appearance, movement_mult=False, move_location=Fal
     return out
 
 
+def _normalize_kp_anchored(kp_video, mean_v, var_v, mean_a, var_a, movement_mult, move_location, clip_mean, adapt, anchor):
+    b, d, k, _ = mean_v.shape
+    has_var = var_v is not None
+    anchor.prepare(b, k, has_var, mean_v.device)
+    area_a = None
+    if movement_mult:
+        area_a = anchor.source_area
+        if area_a is None:
+            area_a = torch.empty(1, dtype=torch.float32, device=mean_v.device)
+            mops._call("mnk_kp_hull_area", mean_v, mops._p(mean_a), k, mops._p(area_a))  # kp_appearance['mean'][0, 0]
+    area_v = anchor.area if movement_mult else None
+    mops._call("mnk_kp_anchor_update", mean_v, mops._p(mean_v), mops._p(var_v), b, d, k, int(movement_mult), mops._p(anchor.mean),
+               mops._p(anchor.var), mops._p(area_v), mops._p(anchor.flag))
+    mean_out = torch.empty_like(mean_v)
+    var_out = torch.empty_like(var_v) if has_var else None
+    mops._call("mnk_kp_normalize_anchored", mean_v, mops._p(mean_v), mops._p(var_v), mops._p(anchor.mean), mops._p(anchor.var),
+               mops._p(mean_a), mops._p(var_a), b, d, k, mops._p(area_a), mops._p(area_v), int(move_location), int(clip_mean),
+               int(adapt), mops._p(mean_out), mops._p(var_out))
+    out = {key: v for key, v in kp_video.items()}
+    out['mean'] = mean_out
+    if has_var:
+        out['var'] = var_out
+    return out
+
+
 class Transfer:
     """transfer.py:65-79 transfer_one without its per-frame Python loops: ONE key-point detector call over all driving
     frames (the detector folds the time axis into the batch), normalize_kp on the device, and ONE generator call with the
@@ -655,10 +687,19 @@ class Transfer:
     key points as they are: the appearance encoder runs once per source instead of once per frame, and its skip tensors
     exist once (B instead of B*d rows); False repeats the source d times along the batch axis.
     precision: "fp32" or "bf16", the ops.inference_precision scope the call runs in (see Reconstructor); fuse_norm: the
-    ops.eval_norm_fusion scope it runs in (see Reconstructor); skinny: the ops.eval_skinny_conv scope (see Reconstructor)."""
+    ops.eval_norm_fusion scope it runs in (see Reconstructor); skinny: the ops.eval_skinny_conv scope (see Reconstructor).
+    chunk=n (with shared_source=True): the call runs a mnk.animation.AnimationSession over ceil(d / n) pushes of n frames and
+    concatenates the results -- the activations of n frames are alive at a time instead of d, the key-points are normalised
+    against frame 0 of the whole video as without chunk."""
 
     def __init__(self, kp_detector, generator, normalization_params, shared_source=False, precision="fp32", fuse_norm=False,
-                 skinny=False):
+                 skinny=False, chunk=None):
+        if chunk is not None:
+            if not shared_source:
+                raise ValueError("chunk requires shared_source=True: the chunks share one encoded source")
+            if int(chunk) != chunk or chunk < 1:
+                raise ValueError("chunk must be a positive number of frames, not %r" % (chunk,))
+        self.chunk = None if chunk is None else int(chunk)
         self.kp_detector, self.generator = kp_detector.eval(), generator.eval()
         self.options = mops.EvalOptions(mops.check_precision(precision), bool(fuse_norm), bool(skinny))
         self.precision, self.fuse_norm, self.skinny = self.options
@@ -666,6 +707,11 @@ class Transfer:
         self.shared_source = bool(shared_source)
 
     def __call__(self, source_image, driving_video):
+        if self.chunk is not None:
+            session = AnimationSession(self.kp_detector, self.generator, self.params, use_graph=False, precision=self.precision,
+                                       fuse_norm=self.fuse_norm, skinny=self.skinny)
+            session.set_source(source_image)
+            return session.animate(driving_video, self.chunk)
         with torch.no_grad(), mops.eval_options(*self.options):
             return self._run(source_image, driving_video)
 
@@ -688,3 +734,4 @@ class Transfer:
 
 
 from .prediction import Prediction, KeyPointPool  # noqa: E402,F401  (the fourth run mode's engine: mnk/prediction.py)
+from .animation import AnimationSession, KpAnchor  # noqa: E402,F401  (sessions over a driving stream: mnk/animation.py)

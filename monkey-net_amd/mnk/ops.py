@@ -956,6 +956,12 @@ def handover_state():
     return {k: v for k, v in slots.items() if v}
 
 
+def pending_outputs():
+    """data pointers of convolution outputs that still wait for the norm layer behind them (a deferred split-K launch's partial sums,
+    a fused launch's hand-through): a tensor kept across calls must not be among them"""
+    return set(_SPLIT_PENDING) | set(_FUSED_PENDING)
+
+
 # ---- what the running backward pass asked for ---------------------------------------------------------------------------------------
 # `ctx.needs_input_grad[i]` of a custom Function says that input i REQUIRES a gradient, not that this pass delivers one:
 # torch.autograd.grad(loss, x) and loss.backward(inputs=[x]) run the node with the flag of every parameter still True.  A returned

@@ -38,12 +38,13 @@ class DenseMotionModule(nn.Module):
         self.use_mask = use_mask
         self.scale_factor = scale_factor
 
-    def field_act(self, source_image, kp_driving, kp_source):
-        """-> sampling field (B*d, h, w, 2) in [-1,1] coordinates (x, y)."""
+    def field_act(self, source_image, kp_driving, kp_source, src_act=None):
+        """-> sampling field (B*d, h, w, 2) in [-1,1] coordinates (x, y).  src_act: the source image already as an act at the
+        mask embedding's resolution (MotionTransferGenerator.encode_source)."""
         step = ops.step_from_scale(self.scale_factor)
         b = source_image.shape[0]
         # MovementEmbeddingModule applies its own scale_factor (1 here) on top of this module's down-scaling
-        pred, c = self.mask_embedding.forward_act(source_image, kp_driving, kp_source, pre_step=step)
+        pred, c = self.mask_embedding.forward_act(source_image, kp_driving, kp_source, src_act=src_act, pre_step=step)
         for block in self.group_blocks:
             pred, c = block.forward_act(pred, c)     # the reference's extra leaky_relu(0.2) after ReLU is the identity
         pred, c = self.hourglass.forward_act(pred, c)

@@ -11,6 +11,34 @@ from mnk import ops
 _MODES = {'nearest': 0, 'trilinear': 1}
 
 
+class SourceState:
+    """What MotionTransferGenerator.encode_source keeps of one batch of source images: the appearance encoder's skip acts
+    [(act, channels)], the source as an act, and the down-scaled source acts the two movement embeddings read when they use the
+    deformed source image (None where they do not); B, H, W of the source."""
+    __slots__ = ("skips", "src_act", "mask_src", "emb_src", "B", "H", "W")
+
+    def __init__(self, skips, src_act, mask_src, emb_src, B, H, W):
+        self.skips, self.src_act, self.mask_src, self.emb_src = skips, src_act, mask_src, emb_src
+        self.B, self.H, self.W = B, H, W
+
+    def tensors(self):
+        out = [a for a, _ in self.skips] + [self.src_act, self.mask_src, self.emb_src]
+        seen, uniq = set(), []
+        for t in out:                        # (the first skip IS the source act)
+            if t is not None and id(t) not in seen:
+                seen.add(id(t))
+                uniq.append(t)
+        return uniq
+
+    def copy_from(self, other):
+        """take another state's values in place (same shapes): captured programs that read this state stay valid"""
+        mine, theirs = self.tensors(), other.tensors()
+        if len(mine) != len(theirs) or any(a.shape != b.shape for a, b in zip(mine, theirs)):
+            raise ValueError("source states of different shapes")
+        for a, b in zip(mine, theirs):
+            a.copy_(b)
+
+
 class MotionTransferGenerator(nn.Module):
     """Given key-points and a source frame, reconstruct the driving frames.  Returns the refined prediction and the
     purely warped source (generator.py:10-82), both (B, C, d, H, W) for d driving frames per source: the source is encoded
@@ -62,7 +90,39 @@ class MotionTransferGenerator(nn.Module):
         out = ops.WarpSkipFn.apply(ops.to_act(inp), field, None, c, 0, self._mode())
         return ops.from_act(out, c, b)
 
-    def forward(self, source_image, kp_driving, kp_source):
+    @torch.no_grad()
+    def encode_source(self, source_image):
+        """Everything forward() computes from the source image alone, for callers that generate from one source over several
+        calls (mnk.engine.AnimationSession): -> SourceState.  Evaluation mode only (a training-mode BatchNorm of the encoder
+        would need the batch of every call).  The state holds activations, not weights: encode again after the weights change."""
+        if self.training:
+            raise RuntimeError("encode_source works in evaluation mode: the appearance encoder's BatchNorm layers would take "
+                               "their statistics from this call's batch")
+        if source_image.dim() != 5 or source_image.shape[2] != 1:
+            raise NotImplementedError("the generator takes one source frame per video; got a source of shape %s"
+                                      % (tuple(source_image.shape),))
+        b, _, _, h, w = source_image.shape
+        src_act = ops.to_act(source_image)
+        skips = self.appearance_encoder.forward_act(src_act, self.num_channels)
+        state = SourceState(skips, src_act, None, None, b, h, w)
+        dm = self.dense_motion_module
+        if isinstance(dm, DenseMotionModule) and dm.mask_embedding.use_deformed_source_image:
+            state.mask_src = ops.to_act(source_image, ops.step_from_scale(dm.mask_embedding.scale_factor)
+                                        * ops.step_from_scale(dm.scale_factor))
+        if self.kp_embedding_module is not None and self.kp_embedding_module.use_deformed_source_image:
+            state.emb_src = ops.to_act(source_image, ops.step_from_scale(self.kp_embedding_module.scale_factor))
+        # every tensor of the state is finished: no split-K partial sum or norm hand-over of mnk.ops may point into it
+        # (the encoder ends in a norm layer, which takes both)
+        pending = ops.pending_outputs()
+        if any(t.data_ptr() in pending for t in state.tensors()):
+            raise RuntimeError("encode_source: an activation of the state still waits for its norm layer")
+        return state
+
+    def forward(self, source_image, kp_driving, kp_source, source_state=None):
+        """source_state: what encode_source(source_image) returned -- the encoder and the source's layout conversions are skipped
+        (evaluation mode; `source_image` then only gives the shapes).  None: everything is computed here."""
+        if source_state is not None:
+            return self._forward_from_state(source_image, kp_driving, kp_source, source_state)
         b = source_image.shape[0]
         d = kp_driving['mean'].shape[1]
         if d < 1 or source_image.shape[2] != 1:
@@ -80,6 +140,30 @@ class MotionTransferGenerator(nn.Module):
             emb, ke = self.kp_embedding_module.forward_act(source_image, kp_driving, kp_source)
         # all warps of this forward as one autograd node: one shared field-gradient buffer (ops.WarpAllFn); the B source
         # rows are shared by the d frames of their video, the outputs have B*d rows
+        return self._decode(b, field, emb, ke, mode, skips, src_act)
+
+    def _forward_from_state(self, source_image, kp_driving, kp_source, state):
+        if self.training:
+            raise RuntimeError("a source state serves evaluation mode only: in training mode the appearance encoder's BatchNorm "
+                               "layers take their statistics from the batch, so the encoder has to run")
+        b, d = source_image.shape[0], kp_driving['mean'].shape[1]
+        if d < 1 or source_image.shape[2] != 1:
+            raise NotImplementedError("the generator takes one source frame per video and d >= 1 driving frames; got %d source "
+                                      "frames, d = %d" % (source_image.shape[2], d))
+        if (b,) + tuple(source_image.shape[3:]) != (state.B, state.H, state.W):
+            raise ValueError("the source state was encoded for (B, H, W) = %s, the source image has %s"
+                             % ((state.B, state.H, state.W), (b,) + tuple(source_image.shape[3:])))
+        mode = self._mode()
+        if isinstance(self.dense_motion_module, DenseMotionModule):
+            field = self.dense_motion_module.field_act(source_image, kp_driving, kp_source, src_act=state.mask_src)
+        else:
+            field = self.dense_motion_module.field_act(source_image, kp_driving, kp_source)
+        emb, ke = None, 0
+        if self.kp_embedding_module is not None:
+            emb, ke = self.kp_embedding_module.forward_act(source_image, kp_driving, kp_source, src_act=state.emb_src)
+        return self._decode(b, field, emb, ke, mode, state.skips, state.src_act)
+
+    def _decode(self, b, field, emb, ke, mode, skips, src_act):
         specs = tuple((c, ke) for _, c in skips) + ((self.num_channels, 0),)
         outs = ops.WarpAllFn.apply(field, emb, mode, specs, *([a for a, _ in skips] + [src_act]))
         warped = [(o, c + ke) for o, (_, c) in zip(outs[:-1], skips)]
