@@ -60,6 +60,16 @@ int mnk_nhwc_to_ncdhw(const float* src, int ld_src, float* dst, int B, int C, in
  * [..., ::step, ::step] get the act's values, every other element 0 (all of dst is written) */
 int mnk_nhwc_to_ncdhw_strided(const float* src, int ld_src, float* dst, int B, int C, int D, int H, int W, int step,
                               void* stream);
+/* uint8 channel-last frames [B][D][H][W][Cs] -- what frames_dataset.py:14-29 read_video starts from -- straight to the act
+ * [(B*D)][H/step][W/step][ld_dst]: Cs = 1 gray replicated to RGB (frames_dataset.py:18-19), Cs = 4 alpha dropped (:21-22),
+ * Cs = 3 as it is; every value img_as_float32's float(byte) * (1.f / 255.f) (:26, the expression of mnk_frames_gather); `step`
+ * picks [::step, ::step] and the pad channels 3 .. ld_dst-1 get 0.f, as in mnk_ncdhw_to_nhwc: the result is, bit for bit,
+ * mnk_ncdhw_to_nhwc of the fp32 (B, 3, D, H, W) tensor of those values. */
+int mnk_u8_to_nhwc(const uint8_t* src, float* dst, int B, int D, int H, int W, int Cs, int step, int ld_dst, void* stream);
+/* the first C channels of the act [rows][ld_src] as uint8 [rows][C] through `(255 * x).astype(np.uint8)` (demo.py:69-71,
+ * reconstruction.py:66-68; the byte conversion of mnk_vis_grid / mnk_frames_to_strip): trunc(255 * mnk_nhwc_to_ncdhw(...))
+ * in channel-last order, byte for byte. */
+int mnk_nhwc_to_u8(const float* src, int ld_src, uint8_t* dst, long rows, int C, void* stream);
 /* dst[r, dst_off + c] = src[r, src_off + c], c < C (torch.cat / slicing: modules/util.py:185, generator.py:73) */
 int mnk_copy_channels(const float* src, int ld_src, int src_off, float* dst, int ld_dst, int dst_off, int C,
                       long rows, int accumulate, void* stream);
@@ -640,6 +650,11 @@ int mnk_conv1x1_fwd(const float* x, int ld_x, int Cin, const float* w, const flo
 int mnk_conv1x1_bwd(const float* x, int ld_x, int Cin, const float* w, const float* out, const float* dout, float* dx,
                     int ld_dx, float* dw, float* dbias, int B, int D, int H, int W, int Cout, int act, float* ws,
                     size_t ws_floats, void* stream);
+/* 'conv-last' + torch.sigmoid (generator.py:48,79-80) written as the uint8 frames the callers save, `(255 * out).astype(np.uint8)`
+ * on (..., H, W, C) (demo.py:69-71, reconstruction.py:66-68): out uint8 [B][D][H][W][Cout].  The same kernels as
+ * mnk_conv1x1_fwd(act = 1), chosen the same way, with a byte epilogue: every byte is trunc(255 * the fp32 entry's value). */
+int mnk_conv1x1_fwd_u8(const float* x, int ld_x, int Cin, const float* w, const float* bias, uint8_t* out, int B, int D, int H,
+                       int W, int Cout, void* stream);
 int mnk_conv1x1_sigmoid_bwd(const float* x, int ld_x, int Cin, const float* w, const float* out, const float* dout,
                             float* dx, int ld_dx, float* dw, float* dbias, int B, int D, int H, int W, int Cout,
                             float* ws, size_t ws_floats, void* stream);

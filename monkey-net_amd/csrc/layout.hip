@@ -1,6 +1,6 @@
 // Layout kernels: (B,C,D,H,W) <-> folded NHWC, channel-slice copies, 2x2 sum-pool, nearest resize.
 // All HBM-bound; one thread per pixel (or per pixel x channel-quad), coalesced along the fastest axis.
-#include "mnk_common.h"
+#include "frame_bytes.h"      // byte_unit, vis_byte: the two frame-byte conversions
 
 using namespace mnk;
 
@@ -43,6 +43,91 @@ __global__ void __launch_bounds__(256) nhwc_to_ncdhw_kernel(const float* __restr
         const float* s = src + i * ld;
         float* o = dst + (((long)b * C * D + d) * H + h) * W + w;
         for (int c = 0; c < C; ++c) o[(long)c * D * H * W] = s[c];
+    }
+}
+
+// ---- uint8 channel-last frames <-> act ------------------------------------------------------------------------------------------
+// frames_dataset.py:14-29 (read_video: gray2rgb, [..., :3], img_as_float32) fused with the (B,C,D,H,W) -> act conversion above, and
+// `(255 * out).astype(np.uint8)` on (..., H, W, C) (demo.py:69-71, reconstruction.py:66-68) fused with the act -> (B,C,D,H,W) one.
+// HBM- and launch-bound byte work: a frame's bytes are a quarter of its fp32 planes and already channel-last.
+//
+// one thread per output pixel, any Cs / step / ld.  DW: Cs == 4 and a 4-byte-aligned source -- the pixel is one dword load;
+// V4: ld % 4 == 0 and a 16-byte-aligned act -- float4 stores.  Pad channels get 0.f, as ncdhw_to_nhwc_kernel writes them.
+template <bool DW, bool V4>
+__global__ void __launch_bounds__(256) u8_to_nhwc_pixel_kernel(const unsigned char* __restrict__ src, float* __restrict__ dst,
+                                                               int B, int D, int H, int W, int Cs, int step, int ld) {
+    const int Ho = H / step, Wo = W / step;
+    const long total = (long)B * D * Ho * Wo;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int wo = (int)(i % Wo);
+        const long t = i / Wo;
+        const int ho = (int)(t % Ho);
+        const long f = t / Ho;                                              // b * D + d
+        const unsigned char* px = src + ((f * H + (long)ho * step) * W + (long)wo * step) * Cs;
+        unsigned r, g, b;
+        if (DW) {
+            const unsigned v = *reinterpret_cast<const unsigned*>(px);      // alpha (bits 24..31) is dropped
+            r = v & 255u, g = (v >> 8) & 255u, b = (v >> 16) & 255u;
+        } else if (Cs >= 3) {
+            r = px[0], g = px[1], b = px[2];
+        } else {
+            r = g = b = px[0];                                              // gray2rgb replicates
+        }
+        float* o = dst + i * ld;
+        if (V4) {
+            *reinterpret_cast<float4*>(o) = make_float4(byte_unit(r), byte_unit(g), byte_unit(b), 0.f);
+            for (int c = 4; c < ld; c += 4) *reinterpret_cast<float4*>(o + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+        } else {
+            o[0] = byte_unit(r), o[1] = byte_unit(g), o[2] = byte_unit(b);
+            for (int c = 3; c < ld; ++c) o[c] = 0.f;
+        }
+    }
+}
+
+// RGB at step 1: the frames are one flat run of pixels.  A thread owns 4 of them: three dword loads (12 bytes), four float4
+// stores per 4 channels of ld.  Needs a pixel count that is a multiple of 4, a 4-byte-aligned source, a 16-byte-aligned act
+// and ld % 4 == 0.
+__global__ void __launch_bounds__(256) u8_to_nhwc_rgb4_kernel(const unsigned* __restrict__ src, float* __restrict__ dst, long quads,
+                                                              int ld) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < quads; i += (long)gridDim.x * blockDim.x) {
+        const unsigned w0 = src[3 * i], w1 = src[3 * i + 1], w2 = src[3 * i + 2];
+        const unsigned p[4] = {w0, (w0 >> 24) | (w1 << 8), (w1 >> 16) | (w2 << 16), w2 >> 8};   // r | g << 8 | b << 16 | (junk)
+        float* o = dst + 4 * i * ld;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            *reinterpret_cast<float4*>(o + (long)j * ld) =
+                make_float4(byte_unit(p[j] & 255u), byte_unit((p[j] >> 8) & 255u), byte_unit((p[j] >> 16) & 255u), 0.f);
+            for (int c = 4; c < ld; c += 4) *reinterpret_cast<float4*>(o + (long)j * ld + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
+}
+
+// act rows -> bytes [rows][C].  VEC (C == 3, ld % 4 == 0, 16-byte-aligned act, 4-byte-aligned bytes): a thread owns 4 rows -- four
+// float4 loads, three packed dword stores -- and the thread behind the last whole group writes the rows % 4 tail by bytes.
+template <bool VEC>
+__global__ void __launch_bounds__(256) nhwc_to_u8_kernel(const float* __restrict__ src, int ld, unsigned char* __restrict__ dst,
+                                                         long rows, int C) {
+    if (VEC) {
+        const long groups = rows >> 2;
+        for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i <= groups; i += (long)gridDim.x * blockDim.x) {
+            if (i < groups) {
+                unsigned by[12];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float4 x = *reinterpret_cast<const float4*>(src + (4 * i + j) * ld);
+                    by[3 * j] = vis_byte(x.x), by[3 * j + 1] = vis_byte(x.y), by[3 * j + 2] = vis_byte(x.z);
+                }
+                unsigned* o32 = reinterpret_cast<unsigned*>(dst + 12 * i);
+#pragma unroll
+                for (int t = 0; t < 3; ++t) o32[t] = by[4 * t] | (by[4 * t + 1] << 8) | (by[4 * t + 2] << 16) | (by[4 * t + 3] << 24);
+            } else {
+                for (long r = 4 * groups; r < rows; ++r)
+                    for (int c = 0; c < 3; ++c) dst[r * 3 + c] = (unsigned char)vis_byte(src[r * ld + c]);
+            }
+        }
+    } else {
+        for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += (long)gridDim.x * blockDim.x)
+            for (int c = 0; c < C; ++c) dst[r * C + c] = (unsigned char)vis_byte(src[r * ld + c]);
     }
 }
 
@@ -444,6 +529,43 @@ int mnk_resize_bilinear_bwd(const float* ddst, int ld_dst, int dst_off, int Hd, 
     ProfScope prof(K_LAYOUT, s, (double)N * Hd * Wd * C * 8);
     hipLaunchKernelGGL(resize_bilinear_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, s, ddst, ld_dst, dst_off, Hd,
                        Wd, dsrc, ld_src, Hs, Ws, N, C);
+    MNK_LAUNCH_CHECK();
+    return MNK_OK;
+}
+
+int mnk_u8_to_nhwc(const uint8_t* src, float* dst, int B, int D, int H, int W, int Cs, int step, int ld_dst, void* stream) {
+    MNK_REQUIRE(src && dst && B > 0 && D > 0 && H > 0 && W > 0 && (Cs == 1 || Cs == 3 || Cs == 4) && step >= 1 && ld_dst >= 3);
+    MNK_REQUIRE(H / step > 0 && W / step > 0);
+    hipStream_t s = (hipStream_t)stream;
+    const long total = (long)B * D * (H / step) * (W / step);
+    ProfScope prof(K_LAYOUT, s, (double)total * (Cs + 4.0 * ld_dst));
+    const bool v4 = ld_dst % 4 == 0 && ptr_aligned(dst, 16), src4 = ptr_aligned(src, 4);
+    const unsigned char* p = (const unsigned char*)src;
+    if (Cs == 3 && step == 1 && total % 4 == 0 && v4 && src4)
+        hipLaunchKernelGGL(u8_to_nhwc_rgb4_kernel, dim3(grid_for(total / 4)), dim3(256), 0, s, (const unsigned*)src, dst, total / 4,
+                           ld_dst);
+    else if (Cs == 4 && v4 && src4)
+        hipLaunchKernelGGL((u8_to_nhwc_pixel_kernel<true, true>), dim3(grid_for(total)), dim3(256), 0, s, p, dst, B, D, H, W, Cs, step,
+                           ld_dst);
+    else if (v4)
+        hipLaunchKernelGGL((u8_to_nhwc_pixel_kernel<false, true>), dim3(grid_for(total)), dim3(256), 0, s, p, dst, B, D, H, W, Cs, step,
+                           ld_dst);
+    else
+        hipLaunchKernelGGL((u8_to_nhwc_pixel_kernel<false, false>), dim3(grid_for(total)), dim3(256), 0, s, p, dst, B, D, H, W, Cs, step,
+                           ld_dst);
+    MNK_LAUNCH_CHECK();
+    return MNK_OK;
+}
+
+int mnk_nhwc_to_u8(const float* src, int ld_src, uint8_t* dst, long rows, int C, void* stream) {
+    MNK_REQUIRE(src && dst && rows > 0 && C > 0 && ld_src >= C);
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(K_LAYOUT, s, (double)rows * C * 5.0);
+    if (C == 3 && ld_src % 4 == 0 && ptr_aligned(src, 16) && ptr_aligned(dst, 4))
+        hipLaunchKernelGGL(nhwc_to_u8_kernel<true>, dim3(grid_for(rows / 4 + 1)), dim3(256), 0, s, src, ld_src, (unsigned char*)dst,
+                           rows, C);
+    else
+        hipLaunchKernelGGL(nhwc_to_u8_kernel<false>, dim3(grid_for(rows)), dim3(256), 0, s, src, ld_src, (unsigned char*)dst, rows, C);
     MNK_LAUNCH_CHECK();
     return MNK_OK;
 }

@@ -6,7 +6,7 @@
 // All HBM-bound element-wise / small-reduction kernels.
 #include <algorithm>
 
-#include "mnk_common.h"
+#include "frame_bytes.h"      // vis_byte: the byte epilogue of the 1x1 + sigmoid kernels
 
 using namespace mnk;
 
@@ -32,6 +32,24 @@ __device__ __forceinline__ void c11_stage(const float* __restrict__ x, int ld_x,
         const float4 v = src[i];
         const int row = i / qpr, q = i - row * qpr;
         *reinterpret_cast<float4*>(&tile[row * ldp + 4 * q]) = v;
+    }
+}
+
+// The byte epilogue of the three 1x1 + sigmoid forward kernels (U8: out is uint8 [rows][Cout], `(255 * sigmoid).astype(np.uint8)` on
+// channel-last frames, demo.py:69-71): the owners of a block's values leave their bytes in LDS -- `ob`, [row of the block][Cout] --
+// and the block writes the contiguous piece it covers, nbytes from `dst`, as packed dwords (every block starts at a row that is
+// a multiple of 4, so the piece of a 4-byte-aligned tensor starts on a dword) with a byte tail.  Called by every thread.
+constexpr int C11_OB = 256 * MAXCO;          // bytes: the widest block piece (a row per thread)
+__device__ __forceinline__ void c11_flush_u8(const unsigned char* ob, int nbytes, unsigned char* __restrict__ dst) {
+    __syncthreads();
+    if (((size_t)dst & 3) == 0) {
+        const int ndw = nbytes >> 2;
+        const unsigned* ob32 = reinterpret_cast<const unsigned*>(ob);
+        unsigned* d32 = reinterpret_cast<unsigned*>(dst);
+        for (int i = threadIdx.x; i < ndw; i += 256) d32[i] = ob32[i];
+        for (int i = (ndw << 2) + threadIdx.x; i < nbytes; i += 256) dst[i] = ob[i];
+    } else {
+        for (int i = threadIdx.x; i < nbytes; i += 256) dst[i] = ob[i];
     }
 }
 
@@ -244,31 +262,55 @@ __global__ void __launch_bounds__(256) gconv1x1_wgrad_final_kernel(const float* 
 }
 
 // ---- 1x1 + sigmoid ---------------------------------------------------------------------------------------------
+// OutT = float: out (B, Cout, D, H, W); unsigned char: out [rows][Cout] bytes (c11_flush_u8) of the same values
+template <typename OutT>
 __global__ void __launch_bounds__(256) conv1x1_sigmoid_fwd_kernel(const float* __restrict__ x, int ld_x, int Cin,
                                                                   const float* __restrict__ w,
                                                                   const float* __restrict__ bias,
-                                                                  float* __restrict__ out, int B, int D, int H, int W,
+                                                                  OutT* __restrict__ out, int B, int D, int H, int W,
                                                                   int Cout, int act) {
+    constexpr bool U8 = sizeof(OutT) == 1;
     const long HW = (long)H * W;
     const long rows = (long)B * D * HW;
-    for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += (long)gridDim.x * blockDim.x) {
+    // (the block walks whole pieces of 256 rows: the trip count is the same for its threads)
+    for (long r0 = (long)blockIdx.x * blockDim.x; r0 < rows; r0 += (long)gridDim.x * blockDim.x) {
+        const long r = r0 + threadIdx.x;
         float acc[MAXCO];
+        if (r < rows) {
 #pragma unroll
-        for (int c = 0; c < MAXCO; ++c) acc[c] = (bias && c < Cout) ? bias[c] : 0.f;
-        const float* xr = x + r * ld_x;
-        for (int k = 0; k < Cin; ++k) {
-            const float v = xr[k];
+            for (int c = 0; c < MAXCO; ++c) acc[c] = (bias && c < Cout) ? bias[c] : 0.f;
+            const float* xr = x + r * ld_x;
+            for (int k = 0; k < Cin; ++k) {
+                const float v = xr[k];
+#pragma unroll
+                for (int c = 0; c < MAXCO; ++c)
+                    if (c < Cout) acc[c] = fmaf(v, w[c * Cin + k], acc[c]);
+            }
 #pragma unroll
             for (int c = 0; c < MAXCO; ++c)
-                if (c < Cout) acc[c] = fmaf(v, w[c * Cin + k], acc[c]);
+                if (c < Cout) acc[c] = act ? 1.f / (1.f + expf(-acc[c])) : acc[c];
         }
-        const long hw = r % HW;
-        const long f = r / HW;
-        const int d = (int)(f % D);
-        const long b = f / D;
+        if constexpr (!U8) {
+            if (r < rows) {
+                const long hw = r % HW;
+                const long f = r / HW;
+                const int d = (int)(f % D);
+                const long b = f / D;
 #pragma unroll
-        for (int c = 0; c < MAXCO; ++c)
-            if (c < Cout) out[((b * Cout + c) * D + d) * HW + hw] = act ? 1.f / (1.f + expf(-acc[c])) : acc[c];
+                for (int c = 0; c < MAXCO; ++c)
+                    if (c < Cout) out[((b * Cout + c) * D + d) * HW + hw] = acc[c];
+            }
+        } else {
+            __shared__ __attribute__((aligned(4))) unsigned char ob[C11_OB];
+            if (r < rows) {
+#pragma unroll
+                for (int c = 0; c < MAXCO; ++c)
+                    if (c < Cout) ob[threadIdx.x * Cout + c] = (unsigned char)vis_byte(acc[c]);
+            }
+            const long left = rows - r0;
+            c11_flush_u8(ob, (int)(left < 256 ? left : 256) * Cout, out + r0 * Cout);
+            __syncthreads();                    // the next piece's bytes go to the same LDS
+        }
     }
 }
 
@@ -387,35 +429,47 @@ __global__ void __launch_bounds__(256) conv1x1_sigmoid_wgrad_final_kernel(const 
 
 // ---- 1x1, few rows x many channels (the discriminator's score head: 64 rows x 512 channels) ---------------------------
 // one wavefront per pixel row (a thread per row walks 512 channels alone: 38 us for 128 KB of input)
+template <typename OutT>
 __global__ void __launch_bounds__(256) conv1x1_wave_fwd_kernel(const float* __restrict__ x, int ld_x, int Cin,
                                                                const float* __restrict__ w, const float* __restrict__ bias,
-                                                               float* __restrict__ out, int B, int D, int H, int W, int Cout,
+                                                               OutT* __restrict__ out, int B, int D, int H, int W, int Cout,
                                                                int act) {
+    constexpr bool U8 = sizeof(OutT) == 1;
     const long HW = (long)H * W, rows = (long)B * D * HW;
-    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long r0 = (long)blockIdx.x * 4, r = r0 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
-    if (r >= rows) return;
-    float acc[MAXCO];
+    __shared__ __attribute__((aligned(4))) unsigned char ob[U8 ? 4 * MAXCO : 4];
+    if (r < rows) {                             // (wave-uniform)
+        float acc[MAXCO];
 #pragma unroll
-    for (int c = 0; c < MAXCO; ++c) acc[c] = 0.f;
-    const float* xr = x + r * ld_x;
-    for (int k = lane; k < Cin; k += 64) {
-        const float v = xr[k];
+        for (int c = 0; c < MAXCO; ++c) acc[c] = 0.f;
+        const float* xr = x + r * ld_x;
+        for (int k = lane; k < Cin; k += 64) {
+            const float v = xr[k];
 #pragma unroll
-        for (int c = 0; c < MAXCO; ++c)
-            if (c < Cout) acc[c] = fmaf(v, w[c * Cin + k], acc[c]);
-    }
-    const long hw = r % HW, f = r / HW;
-    const int d = (int)(f % D);
-    const long b = f / D;
-#pragma unroll
-    for (int c = 0; c < MAXCO; ++c) {
-        if (c >= Cout) continue;
-        float v = wave_sum(acc[c]);
-        if (lane == 0) {
-            v += bias ? bias[c] : 0.f;
-            out[((b * Cout + c) * D + d) * HW + hw] = act ? 1.f / (1.f + expf(-v)) : v;
+            for (int c = 0; c < MAXCO; ++c)
+                if (c < Cout) acc[c] = fmaf(v, w[c * Cin + k], acc[c]);
         }
+        const long hw = r % HW, f = r / HW;
+        const int d = (int)(f % D);
+        const long b = f / D;
+#pragma unroll
+        for (int c = 0; c < MAXCO; ++c) {
+            if (c >= Cout) continue;
+            float v = wave_sum(acc[c]);
+            if (lane == 0) {
+                v += bias ? bias[c] : 0.f;
+                v = act ? 1.f / (1.f + expf(-v)) : v;
+                if constexpr (U8)
+                    ob[(threadIdx.x >> 6) * Cout + c] = (unsigned char)vis_byte(v);
+                else
+                    out[((b * Cout + c) * D + d) * HW + hw] = v;
+            }
+        }
+    }
+    if constexpr (U8) {
+        const long left = rows - r0;
+        c11_flush_u8(ob, (int)(left < 4 ? left : 4) * Cout, out + r0 * Cout);
     }
 }
 
@@ -455,11 +509,14 @@ constexpr int C11_TR = 128;                  // pixel rows per tile
 constexpr int C11_MAXLD = 64;                // widest staged row (floats)
 constexpr int C11_LDT = C11_MAXLD + 4;       // LDS row pitch bound
 
+template <typename OutT>
 __global__ void __launch_bounds__(256) conv1x1_rows_fwd_kernel(const float* __restrict__ x, int ld_x, int Cin,
                                                                const float* __restrict__ w, const float* __restrict__ bias,
-                                                               float* __restrict__ out, int B, int D, int H, int W, int Cout,
+                                                               OutT* __restrict__ out, int B, int D, int H, int W, int Cout,
                                                                int act) {
+    constexpr bool U8 = sizeof(OutT) == 1;
     __shared__ __attribute__((aligned(16))) float tile[C11_TR * C11_LDT];
+    __shared__ __attribute__((aligned(4))) unsigned char ob[U8 ? C11_TR * MAXCO : 4];
     const int ldp = ld_x + 4;
     const long HW = (long)H * W, rows = (long)B * D * HW;
     const long r0 = (long)blockIdx.x * C11_TR;
@@ -468,22 +525,31 @@ __global__ void __launch_bounds__(256) conv1x1_rows_fwd_kernel(const float* __re
     __syncthreads();
     // thread = (row, half): the two halves of the block own output channels {0, 1} and {2, 3}
     const int row = threadIdx.x & (C11_TR - 1), c0 = (threadIdx.x >> 7) * 2;
-    if (row >= nrows || c0 >= Cout) return;
-    const bool two = c0 + 1 < Cout;
-    const float* w0 = w + c0 * Cin;
-    const float* w1 = w + (two ? c0 + 1 : c0) * Cin;
-    float a0 = bias ? bias[c0] : 0.f, a1 = (bias && two) ? bias[c0 + 1] : 0.f;
-    const float* xr = tile + row * ldp;
-    for (int k = 0; k < Cin; ++k) {
-        const float v = xr[k];
-        a0 = fmaf(v, w0[k], a0);
-        a1 = fmaf(v, w1[k], a1);
+    if (row < nrows && c0 < Cout) {
+        const bool two = c0 + 1 < Cout;
+        const float* w0 = w + c0 * Cin;
+        const float* w1 = w + (two ? c0 + 1 : c0) * Cin;
+        float a0 = bias ? bias[c0] : 0.f, a1 = (bias && two) ? bias[c0 + 1] : 0.f;
+        const float* xr = tile + row * ldp;
+        for (int k = 0; k < Cin; ++k) {
+            const float v = xr[k];
+            a0 = fmaf(v, w0[k], a0);
+            a1 = fmaf(v, w1[k], a1);
+        }
+        a0 = act ? 1.f / (1.f + expf(-a0)) : a0;
+        if (two) a1 = act ? 1.f / (1.f + expf(-a1)) : a1;
+        if constexpr (U8) {                     // the two halves' bytes of a pixel meet in LDS
+            ob[row * Cout + c0] = (unsigned char)vis_byte(a0);
+            if (two) ob[row * Cout + c0 + 1] = (unsigned char)vis_byte(a1);
+        } else {
+            const long r = r0 + row, hw = r % HW, f = r / HW;
+            const int d = (int)(f % D);
+            const long b = f / D;
+            out[((b * Cout + c0) * D + d) * HW + hw] = a0;
+            if (two) out[((b * Cout + c0 + 1) * D + d) * HW + hw] = a1;
+        }
     }
-    const long r = r0 + row, hw = r % HW, f = r / HW;
-    const int d = (int)(f % D);
-    const long b = f / D;
-    out[((b * Cout + c0) * D + d) * HW + hw] = act ? 1.f / (1.f + expf(-a0)) : a0;
-    if (two) out[((b * Cout + c0 + 1) * D + d) * HW + hw] = act ? 1.f / (1.f + expf(-a1)) : a1;
+    if constexpr (U8) c11_flush_u8(ob, nrows * Cout, out + r0 * Cout);
 }
 
 // dx rows + the weight-gradient partial of the block's row range [blockIdx.x * rows_per_block, ...), tile by tile.
@@ -1533,21 +1599,44 @@ static bool c11_rows_form(const float* x, int ld_x, int Cin) {
     return g_c11_rows && ld_x % 4 == 0 && ld_x <= C11_MAXLD && Cin + 1 <= 128 && (size_t)x % 16 == 0;
 }
 
+}  // extern "C"
+
+// the one choice of a forward form, for the fp32 and the uint8 output alike
+template <typename OutT>
+static void c11_fwd_launch(const float* x, int ld_x, int Cin, const float* w, const float* bias, OutT* out, int B, int D, int H,
+                           int W, int Cout, int act, hipStream_t s) {
+    const long rows = (long)B * D * H * W;
+    if (c11_rows_form(x, ld_x, Cin))
+        hipLaunchKernelGGL(conv1x1_rows_fwd_kernel<OutT>, dim3((unsigned)((rows + C11_TR - 1) / C11_TR)), dim3(256), 0, s, x, ld_x,
+                           Cin, w, bias, out, B, D, H, W, Cout, act);
+    else if (g_c11_rows && Cin >= 64)
+        hipLaunchKernelGGL(conv1x1_wave_fwd_kernel<OutT>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, ld_x, Cin, w, bias,
+                           out, B, D, H, W, Cout, act);
+    else
+        hipLaunchKernelGGL(conv1x1_sigmoid_fwd_kernel<OutT>, dim3(grid_for(rows)), dim3(256), 0, s, x, ld_x, Cin, w, bias, out, B,
+                           D, H, W, Cout, act);
+}
+
+extern "C" {
+
 int mnk_conv1x1_fwd(const float* x, int ld_x, int Cin, const float* w, const float* bias, float* out, int B, int D, int H,
                     int W, int Cout, int act, void* stream) {
     MNK_REQUIRE(x && w && out && B > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cout <= MAXCO && ld_x >= Cin);
     hipStream_t s = (hipStream_t)stream;
     const long rows = (long)B * D * H * W;
     ProfScope prof(K_CONV1X1, s, (double)rows * (Cin + Cout) * 4);
-    if (c11_rows_form(x, ld_x, Cin))
-        hipLaunchKernelGGL(conv1x1_rows_fwd_kernel, dim3((unsigned)((rows + C11_TR - 1) / C11_TR)), dim3(256), 0, s, x, ld_x,
-                           Cin, w, bias, out, B, D, H, W, Cout, act);
-    else if (g_c11_rows && Cin >= 64)
-        hipLaunchKernelGGL(conv1x1_wave_fwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, ld_x, Cin, w, bias,
-                           out, B, D, H, W, Cout, act);
-    else
-        hipLaunchKernelGGL(conv1x1_sigmoid_fwd_kernel, dim3(grid_for(rows)), dim3(256), 0, s, x, ld_x, Cin, w, bias, out, B,
-                           D, H, W, Cout, act);
+    c11_fwd_launch(x, ld_x, Cin, w, bias, out, B, D, H, W, Cout, act, s);
+    MNK_LAUNCH_CHECK();
+    return MNK_OK;
+}
+
+int mnk_conv1x1_fwd_u8(const float* x, int ld_x, int Cin, const float* w, const float* bias, uint8_t* out, int B, int D, int H,
+                       int W, int Cout, void* stream) {
+    MNK_REQUIRE(x && w && out && B > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cout <= MAXCO && ld_x >= Cin);
+    hipStream_t s = (hipStream_t)stream;
+    const long rows = (long)B * D * H * W;
+    ProfScope prof(K_CONV1X1, s, (double)rows * (Cin * 4.0 + Cout));
+    c11_fwd_launch(x, ld_x, Cin, w, bias, (unsigned char*)out, B, D, H, W, Cout, 1, s);
     MNK_LAUNCH_CHECK();
     return MNK_OK;
 }

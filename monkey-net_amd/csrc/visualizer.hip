@@ -12,7 +12,7 @@
 // threads of a wave cover consecutive runs of an output row), reads one float4 per channel plane (coalesced along W) and tests
 // its pixels against the K <= 32 key points of its (column, video, frame) in float64 -- the arithmetic of numpy and
 // scikit-image 0.14, statement by statement, so that every byte equals the reference's.
-#include "mnk_common.h"
+#include "frame_bytes.h"      // vis_byte: `(255 * image).astype(np.uint8)`
 
 using namespace mnk;
 
@@ -27,12 +27,6 @@ constexpr int VIS_RUN = 4;          // output pixels per thread
 struct VisColumns {                 // the column table, by value in the kernel arguments
     MnkVisColumn c[VIS_MAX_COLS];
 };
-
-// `(255 * image).astype(np.uint8)` (logger.py:151, :174): a float32 product (255 is a Python int: the array stays float32),
-// truncated toward zero
-__device__ __forceinline__ unsigned vis_byte(float v) {
-    return (unsigned)(int)__fmul_rn(255.f, v) & 255u;
-}
 
 // One axis of skimage.draw.ellipse's bounding box (scikit-image 0.14, draw.py: upper_left = ceil(center - radii) clipped to 0,
 // lower_right = floor(center + radii) clipped to shape - 1, shifted_center = center - upper_left), all in float64.  The box

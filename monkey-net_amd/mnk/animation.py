@@ -97,10 +97,19 @@ class AnimationSession:
     packed weights and the evaluation-mode norm coefficients of the moment of capture, and is captured again when a parameter, a
     buffer or the optimiser epoch changed -- the cached source is not re-encoded by that: set_source() does it.
     precision / fuse_norm / skinny: one ops.EvalOptions value, as in Reconstructor / Transfer; a captured program keeps the
-    options it was built with."""
+    options it was built with.
+
+    uint8 frames: set_source and push also take an ops.U8Frames or a bare 5-d torch.uint8 tensor, which is taken as channel-last
+    frames (B, n, H, W, C), C = 1 / 3 / 4 -- what a decoder or a camera hands over (frames_dataset.py:14-40).  The bytes go straight
+    into the kernels' layout (mnk_u8_to_nhwc); they may live on the host, pinned or not: the push copies them to the device once, a
+    quarter of the fp32 bytes, and a captured program's static input is that uint8 buffer.
+    output="uint8": video_prediction / video_deformed come back as uint8 (B, n, H, W, C), `(255 * out).astype(np.uint8)`
+    channel-last (demo.py:69-71), written by the generator's last kernels; the fp32 tensors are not made.  Programs are keyed by
+    (B, n) and, where they are not float / float, by the input kind and the output kind."""
 
     def __init__(self, kp_detector, generator, normalization_params=None, use_graph=None, precision="fp32", fuse_norm=False,
-                 skinny=False):
+                 skinny=False, output="float"):
+        self.output = mops.check_output(output)
         self.kp_detector, self.generator = kp_detector.eval(), generator.eval()
         self.options = mops.EvalOptions(mops.check_precision(precision), bool(fuse_norm), bool(skinny))
         self.precision, self.fuse_norm, self.skinny = self.options
@@ -128,6 +137,7 @@ class AnimationSession:
         return on_device if self.use_graph is None else (bool(self.use_graph) and on_device)
 
     def set_source(self, source_image):
+        source_image = mops.as_frames(source_image, mops.module_device(self.generator))
         if source_image.dim() != 5 or source_image.shape[2] != 1:
             raise ValueError("set_source takes (B, C, 1, H, W); got %s" % (tuple(source_image.shape),))
         self._weights = [t for m in (self.kp_detector, self.generator) for t in list(m.parameters()) + list(m.buffers())]
@@ -140,6 +150,7 @@ class AnimationSession:
                 area = torch.empty(1, dtype=torch.float32, device=mean.device)
                 mops._call("mnk_kp_hull_area", mean, mops._p(mean), mean.shape[2], mops._p(area))    # kp_source['mean'][0, 0]
             same = (self._source is not None and self._source.shape == source_image.shape
+                    and mops.frame_kind(self._source) == mops.frame_kind(source_image)
                     and self._source.device == source_image.device and set(self._kp_source) == set(kp_source))
             if same:
                 self._source.copy_(source_image)
@@ -150,7 +161,7 @@ class AnimationSession:
                     self.anchor.source_area.copy_(area)
             else:
                 self._programs.clear()
-                self._source = source_image.detach().float().clone()
+                self._source = source_image.clone() if mops.is_u8(source_image) else source_image.detach().float().clone()
                 self._kp_source = {k: v.clone() for k, v in kp_source.items()}
                 self._state = state
                 self.anchor = KpAnchor()
@@ -171,7 +182,8 @@ class AnimationSession:
             kp_norm = engine.normalize_kp(kp_driving, self._kp_source, anchor=self.anchor, **self.params)
         else:
             kp_norm = {k: v for k, v in kp_driving.items()}
-        out = self.generator(self._source, kp_driving=kp_norm, kp_source=self._kp_source, source_state=self._state)
+        out = self.generator(self._source, kp_driving=kp_norm, kp_source=self._kp_source, source_state=self._state,
+                             output=self.output)
         return {"video_prediction": out["video_prediction"], "video_deformed": out["video_deformed"],
                 "kp_driving": kp_driving, "kp_source": self._kp_source, "kp_norm": kp_norm}
 
@@ -184,7 +196,8 @@ class AnimationSession:
         one included: the anchor and its flag are put back afterwards, so the program starts from the state the session was in.
         Every program of the session warms up and is captured on one stream: the packed-weight and norm-coefficient caches the
         capture reads are keyed by it."""
-        static_in = frames.detach().float().clone()
+        # (uint8 frames stay bytes: the static input is the uint8 buffer, on the device wherever the caller's frames live)
+        static_in = frames.to(self._source.device).clone() if mops.is_u8(frames) else frames.detach().float().clone()
         snap = self.anchor.snapshot()
         if self._cap is None:
             self._cap = torch.cuda.Stream()
@@ -211,6 +224,7 @@ class AnimationSession:
     def push(self, frames):
         if self._state is None:
             raise ValueError("push() before set_source()")
+        frames = mops.as_frames(frames)
         if frames.dim() != 5 or frames.shape[2] < 1:
             raise ValueError("push takes (B, C, n, H, W) with n >= 1; got %s" % (tuple(frames.shape),))
         b, c, n, h, w = frames.shape
@@ -221,14 +235,17 @@ class AnimationSession:
             raise NameError("clip_mean without move_location is an error in the reference too (transfer.py:49)")
         with torch.no_grad(), mops.eval_options(*self.options):
             if self._graph_on():
-                prog, fp = self._programs.get((b, n)), self._fingerprint()
+                # (B, n) for float frames in and out, as ever; other input / output kinds append theirs: (B, n, kind, output)
+                kinds = (mops.frame_kind(frames), self.output)
+                key = (b, n) if kinds == (("float", c), "float") else (b, n) + kinds
+                prog, fp = self._programs.get(key), self._fingerprint()
                 if prog is None or prog[3] != fp:
-                    prog = self._programs[(b, n)] = self._capture(frames, fp)
+                    prog = self._programs[key] = self._capture(frames, fp)
                 graph, static_in, out = prog[:3]
                 static_in.copy_(frames, non_blocking=True)
                 graph.replay()
             else:
-                out = self._forward(frames)
+                out = self._forward(frames.to(self._source.device) if mops.is_u8(frames) else frames)
         self.frames_pushed += n
         return out
 
@@ -237,11 +254,13 @@ class AnimationSession:
         Transfer(shared_source=True) returns for it, with the activations of one chunk alive at a time"""
         self.reset()
         parts = []
+        driving_video = mops.as_frames(driving_video)
         for i in range(0, driving_video.shape[2], chunk):
             out = self.push(driving_video[:, :, i:i + chunk])
             parts.append({k: (v.clone() if torch.is_tensor(v) else {kk: t.clone() for kk, t in v.items()}) for k, v in out.items()}
                          if self._graph_on() else out)
-        return {"video_prediction": torch.cat([p["video_prediction"] for p in parts], dim=2),
-                "video_deformed": torch.cat([p["video_deformed"] for p in parts], dim=2),
+        fdim = 1 if self.output == "uint8" else 2            # the frame axis of (B, n, H, W, C) / (B, C, n, H, W)
+        return {"video_prediction": torch.cat([p["video_prediction"] for p in parts], dim=fdim),
+                "video_deformed": torch.cat([p["video_deformed"] for p in parts], dim=fdim),
                 "kp_driving": _cat_kp([p["kp_driving"] for p in parts]), "kp_source": parts[0]["kp_source"],
                 "kp_norm": _cat_kp([p["kp_norm"] for p in parts])}

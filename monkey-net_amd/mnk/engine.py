@@ -568,14 +568,18 @@ class Reconstructor:
     layer, ReLU and pool behind them in their own epilogue; the outputs are equal to the default's.  A
     captured graph keeps the form it was built with.
     skinny: the forward runs inside ops.eval_skinny_conv(skinny): conv -> norm pairs with few output rows (batch 1: the deep
-    hourglass levels) run as weight-streaming launches; a batched call has no such layer and is unchanged."""
+    hourglass levels) run as weight-streaming launches; a batched call has no such layer and is unchanged.
+    source / driving: fp32 (B, C, d, H, W), an ops.U8Frames, or a bare 5-d torch.uint8 tensor = channel-last frames (B, d, H, W, C)
+    on the device or the host; output="uint8": the two videos as uint8 (B, d, H, W, C) (see mnk.animation.AnimationSession)."""
 
-    def __init__(self, kp_detector, generator, use_graph=False, precision="fp32", fuse_norm=False, skinny=False):
+    def __init__(self, kp_detector, generator, use_graph=False, precision="fp32", fuse_norm=False, skinny=False, output="float"):
+        self.output = mops.check_output(output)
         self.kp_detector, self.generator = kp_detector.eval(), generator.eval()
         self.options = mops.EvalOptions(mops.check_precision(precision), bool(fuse_norm), bool(skinny))
         self.precision, self.fuse_norm, self.skinny = self.options
         self.use_graph = bool(use_graph)
         self._graph = None
+        self._kinds = None
         self._static_in = None
         self._static_out = None
 
@@ -584,18 +588,22 @@ class Reconstructor:
         with mops.eval_options(*self.options):
             kp_source = self.kp_detector(source)
             kp_driving = self.kp_detector(driving)
-            out = self.generator(source, kp_driving=kp_driving, kp_source=kp_source)
+            out = self.generator(source, kp_driving=kp_driving, kp_source=kp_source, output=self.output)
         return {"video_prediction": out["video_prediction"], "video_deformed": out["video_deformed"],
                 "kp_driving_mean": kp_driving["mean"], "kp_source_mean": kp_source["mean"]}
 
     def __call__(self, source, driving):
+        device = mops.module_device(self.generator)
         if not self.use_graph:
-            return self._forward(source, driving)
-        if self._graph is None or self._static_in[0].shape != source.shape:
+            return self._forward(mops.as_frames(source, device), mops.as_frames(driving, device))
+        source, driving = mops.as_frames(source), mops.as_frames(driving)        # (host bytes go straight to the static inputs)
+        kinds = (mops.frame_kind(source), mops.frame_kind(driving))
+        if self._graph is None or self._static_in[0].shape != source.shape or self._kinds != kinds:
+            self._kinds = kinds
             # the captured forward contains its own weight-pack launches (ops._packed_fwd_weight under capture), so a
             # replay always runs on the live parameters: optimiser steps, load_state_dict and in-place writes need no
             # re-capture
-            self._static_in = (source.clone(), driving.clone())
+            self._static_in = tuple(mops.as_frames(t, device).clone() for t in (source, driving))
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
@@ -690,10 +698,14 @@ class Transfer:
     ops.eval_norm_fusion scope it runs in (see Reconstructor); skinny: the ops.eval_skinny_conv scope (see Reconstructor).
     chunk=n (with shared_source=True): the call runs a mnk.animation.AnimationSession over ceil(d / n) pushes of n frames and
     concatenates the results -- the activations of n frames are alive at a time instead of d, the key-points are normalised
-    against frame 0 of the whole video as without chunk."""
+    against frame 0 of the whole video as without chunk.
+    source_image / driving_video: fp32 (B, C, d, H, W), an ops.U8Frames, or a bare 5-d torch.uint8 tensor = channel-last frames
+    (B, d, H, W, C) on the device or the host (shared_source=False repeats the source's BYTES); output="uint8": the two videos as
+    uint8 (B, d, H, W, C) (see mnk.animation.AnimationSession)."""
 
     def __init__(self, kp_detector, generator, normalization_params, shared_source=False, precision="fp32", fuse_norm=False,
-                 skinny=False, chunk=None):
+                 skinny=False, chunk=None, output="float"):
+        self.output = mops.check_output(output)
         if chunk is not None:
             if not shared_source:
                 raise ValueError("chunk requires shared_source=True: the chunks share one encoded source")
@@ -709,11 +721,12 @@ class Transfer:
     def __call__(self, source_image, driving_video):
         if self.chunk is not None:
             session = AnimationSession(self.kp_detector, self.generator, self.params, use_graph=False, precision=self.precision,
-                                       fuse_norm=self.fuse_norm, skinny=self.skinny)
+                                       fuse_norm=self.fuse_norm, skinny=self.skinny, output=self.output)
             session.set_source(source_image)
             return session.animate(driving_video, self.chunk)
+        device = mops.module_device(self.generator)
         with torch.no_grad(), mops.eval_options(*self.options):
-            return self._run(source_image, driving_video)
+            return self._run(mops.as_frames(source_image, device), mops.as_frames(driving_video, device))
 
     def _run(self, source_image, driving_video):
         b, c, d, h, w = driving_video.shape
@@ -721,14 +734,17 @@ class Transfer:
         kp_source = self.kp_detector(source_image)                       # (B, 1, K, .)
         kp_norm = normalize_kp(kp_driving, kp_source, **self.params)
         if self.shared_source:
-            out = self.generator(source_image, kp_driving=kp_norm, kp_source=kp_source)          # both (B, C, d, H, W)
+            out = self.generator(source_image, kp_driving=kp_norm, kp_source=kp_source, output=self.output)  # (B, C, d, H, W)
             return {"video_prediction": out["video_prediction"], "video_deformed": out["video_deformed"],
                     "kp_driving": kp_driving, "kp_source": kp_source, "kp_norm": kp_norm}
         fold = lambda t: t.reshape((b * d, 1) + t.shape[2:])             # frame f of video v -> batch entry v * d + f
         rep = lambda t: t.repeat_interleave(d, dim=0)
         out = self.generator(rep(source_image), kp_driving={k: fold(v) for k, v in kp_norm.items()},
-                             kp_source={k: rep(v) for k, v in kp_source.items()})
-        unfold = lambda t: t.reshape(b, d, c, h, w).permute(0, 2, 1, 3, 4)       # (B*d, C, 1, H, W) -> (B, C, d, H, W)
+                             kp_source={k: rep(v) for k, v in kp_source.items()}, output=self.output)
+        if self.output == "uint8":
+            unfold = lambda t: t.reshape(b, d, h, w, c)                          # (B*d, 1, H, W, C) -> (B, d, H, W, C)
+        else:
+            unfold = lambda t: t.reshape(b, d, c, h, w).permute(0, 2, 1, 3, 4)   # (B*d, C, 1, H, W) -> (B, C, d, H, W)
         return {"video_prediction": unfold(out["video_prediction"]), "video_deformed": unfold(out["video_deformed"]),
                 "kp_driving": kp_driving, "kp_source": kp_source, "kp_norm": kp_norm}
 

@@ -153,6 +153,152 @@ class StackedBatch:
         return torch.cat(self.parts, dim=0)[idx]
 
 
+OUTPUT_KINDS = ("float", "uint8")
+
+
+def check_output(output):
+    if output not in OUTPUT_KINDS:
+        raise ValueError('output must be "float" (fp32 (B, C, d, H, W), the default) or "uint8" (channel-last (B, d, H, W, C) '
+                         'frames); got %r' % (output,))
+    return output
+
+
+class U8Frames:
+    """uint8 channel-last frames (B, n, H, W, Cs) -- what imageio, a decoder or a camera hand over (frames_dataset.py:14-40
+    read_video) -- standing where the modules take the fp32 (B, 3, n, H, W) tensor of `img_as_float32` of them: gray (Cs = 1) is
+    replicated to RGB, alpha (Cs = 4) is dropped.  It presents that tensor's shape, dim(), device and type(); the only consumer of
+    its values is to_act, which converts the bytes straight into the kernels' layout (mnk_u8_to_nhwc): no fp32 copy of the frames
+    exists.  Inference only: the modules refuse it in training mode, and under grad mode when a parameter requires grad.
+    float(): the fp32 (B, 3, n, H, W) tensor of the same values (comparison paths, callers that need the tensor)."""
+
+    def __init__(self, data):
+        if not torch.is_tensor(data) or data.dtype != torch.uint8:
+            raise ValueError("U8Frames takes a torch.uint8 tensor (B, n, H, W, C); got %s"
+                             % (data.dtype if torch.is_tensor(data) else type(data).__name__,))
+        if data.dim() != 5:
+            raise ValueError("uint8 frames are channel-last (B, n, H, W, C) -- add the batch / frame axes with [None]; got %d-d %s"
+                             % (data.dim(), tuple(data.shape)))
+        if data.shape[4] not in (1, 3, 4):
+            raise ValueError("uint8 frames have C = 1 (gray), 3 (RGB) or 4 (RGBA) channels in the LAST axis; got %s -- a channel-"
+                             "first array needs .permute(0, 2, 3, 4, 1) first" % (tuple(data.shape),))
+        self.data = data.contiguous()
+        b, n, h, w, _ = data.shape
+        self.shape = torch.Size((b, 3, n, h, w))
+
+    device = property(lambda self: self.data.device)
+    channels = property(lambda self: self.data.shape[4])
+    kind = property(lambda self: ("uint8", self.data.shape[4]))
+
+    def dim(self):
+        return 5
+
+    def size(self, i=None):
+        return self.shape if i is None else self.shape[i]
+
+    def type(self):
+        return "torch.cuda.FloatTensor" if self.data.is_cuda else "torch.FloatTensor"
+
+    def detach(self):
+        return self
+
+    def contiguous(self):
+        return self
+
+    def clone(self):
+        return U8Frames(self.data.clone())
+
+    def to(self, device, non_blocking=False):
+        return self if self.data.device == torch.device(device) else U8Frames(self.data.to(device, non_blocking=non_blocking))
+
+    def copy_(self, other, non_blocking=False):
+        self.data.copy_(other.data, non_blocking=non_blocking)
+        return self
+
+    def repeat_interleave(self, repeats, dim=0):
+        if dim != 0:
+            raise NotImplementedError("U8Frames repeats along the batch axis only")
+        return U8Frames(self.data.repeat_interleave(repeats, dim=0))
+
+    def __getitem__(self, idx):
+        """frames[:, :, i:j] (and batch slices): the same frames of the (B, 3, n, H, W) view, still as bytes"""
+        idx = idx if isinstance(idx, tuple) else (idx,)
+        if len(idx) > 3 or not all(isinstance(i, slice) for i in idx) or (len(idx) > 1 and idx[1] != slice(None)):
+            raise NotImplementedError("U8Frames takes slices of the batch and the frame axis: frames[b0:b1, :, f0:f1]")
+        data = self.data[idx[0]]
+        return U8Frames(data[:, idx[2]] if len(idx) == 3 else data)
+
+    def float(self):
+        rgb = self.data.expand(-1, -1, -1, -1, 3) if self.data.shape[4] == 1 else self.data[..., :3]
+        # img_as_float32: uint8 * float32(1 / 255), one fp32 product per value
+        return (rgb.permute(0, 4, 1, 2, 3).float() * torch.tensor(1.0 / 255.0, dtype=torch.float32, device=rgb.device)).contiguous()
+
+
+def is_u8(x):
+    return isinstance(x, U8Frames)
+
+
+def frame_kind(x):
+    """what a captured program's static input is keyed by"""
+    return x.kind if isinstance(x, U8Frames) else ("float", x.shape[1])
+
+
+def as_frames(x, device=None):
+    """What the engines take as frames: a float (B, C, n, H, W) tensor (as it is), a U8Frames, or a bare 5-d torch.uint8 tensor,
+    which is taken as channel-last frames (B, n, H, W, C) and wrapped.  device: uint8 frames that live elsewhere (the host, pinned
+    or not) are copied there -- the bytes, once."""
+    if torch.is_tensor(x) and x.dtype == torch.uint8:
+        x = U8Frames(x)
+    if isinstance(x, U8Frames) and device is not None:
+        x = x.to(device, non_blocking=True)
+    return x
+
+
+def module_device(module):
+    """where a module's parameters live (None for a module without any): where host-resident uint8 frames are copied to"""
+    p = next(module.parameters(), None)
+    return None if p is None else p.device
+
+
+def require_inference(module, x, what="uint8 frames"):
+    """uint8 frames (and uint8 outputs) carry no gradient: evaluation mode, and no grad mode while a parameter requires grad"""
+    if module.training:
+        raise RuntimeError("%s serve inference only and %s is in training mode: call .eval() first (or pass the fp32 tensor, "
+                           "U8Frames.float())" % (what, type(module).__name__))
+    if torch.is_grad_enabled() and any(p.requires_grad for p in module.parameters()):
+        raise RuntimeError("%s serve inference only and %s has parameters that require grad under an enabled grad mode: wrap the "
+                           "call in torch.no_grad() (or pass the fp32 tensor, U8Frames.float())" % (what, type(module).__name__))
+
+
+def u8_to_act(x, step=1):
+    """U8Frames -> act, with the nearest down-scaling by `step`: bit for bit ToActFn of x.float(), pad lanes included"""
+    data = x.data
+    _check_device(data)
+    b, n, h, w, cs = data.shape
+    out = torch.empty(b * n, h // step, w // step, 4, dtype=torch.float32, device=data.device)
+    _call("mnk_u8_to_nhwc", data, _p(data), _p(out), b, n, h, w, cs, int(step), 4)
+    return out
+
+
+def act_to_u8(a, c, b):
+    """act -> uint8 (B, d, H, W, C) = `(255 * from_act(a, c, b)).to(uint8)` channel-last (demo.py:69-71)"""
+    _check_device(a)
+    n, h, w, ld = a.shape
+    out = torch.empty(b, n // b, h, w, c, dtype=torch.uint8, device=a.device)
+    _call("mnk_nhwc_to_u8", a, _p(a), ld, _p(out), n * h * w, c)
+    return out
+
+
+def conv1x1_sigmoid_u8(x, weight, bias, cin, b):
+    """Conv1x1SigmoidFn's forward (act = 1) written as uint8 (B, d, H, W, Cout): the same kernel with a byte epilogue.
+    No autograd node: the caller is in evaluation mode under no_grad."""
+    _check_device(x)
+    n, h, w, ld = x.shape
+    cout = weight.shape[0]
+    out = torch.empty(b, n // b, h, w, cout, dtype=torch.uint8, device=x.device)
+    _call("mnk_conv1x1_fwd_u8", x, _p(x), ld, cin, _p(weight), _p(bias), _p(out), b, n // b, h, w, cout)
+    return out
+
+
 class ToActPairFn(_Fn):
     """ToActFn of StackedBatch(a, b): one act, its two halves written by one conversion launch each."""
 
@@ -2421,6 +2567,8 @@ class WarpAllFn(_Fn):
 
 # convenience wrappers ---------------------------------------------------------------------------------------------
 def to_act(x5, step=1):
+    if isinstance(x5, U8Frames):
+        return u8_to_act(x5, int(step))
     if isinstance(x5, StackedBatch):
         return ToActPairFn.apply(x5.parts[0], x5.parts[1], step)
     return ToActFn.apply(x5, int(step))

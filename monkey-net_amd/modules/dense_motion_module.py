@@ -41,6 +41,8 @@ class DenseMotionModule(nn.Module):
     def field_act(self, source_image, kp_driving, kp_source, src_act=None):
         """-> sampling field (B*d, h, w, 2) in [-1,1] coordinates (x, y).  src_act: the source image already as an act at the
         mask embedding's resolution (MotionTransferGenerator.encode_source)."""
+        if ops.is_u8(source_image):          # uint8 frames (ops.U8Frames): read through ops.to_act by the mask embedding
+            ops.require_inference(self, source_image)
         step = ops.step_from_scale(self.scale_factor)
         b = source_image.shape[0]
         # MovementEmbeddingModule applies its own scale_factor (1 here) on top of this module's down-scaling

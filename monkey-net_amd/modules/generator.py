@@ -41,7 +41,8 @@ class SourceState:
 
 class MotionTransferGenerator(nn.Module):
     """Given key-points and a source frame, reconstruct the driving frames.  Returns the refined prediction and the
-    purely warped source (generator.py:10-82), both (B, C, d, H, W) for d driving frames per source: the source is encoded
+    purely warped source (generator.py:10-82), both (B, C, d, H, W) for d driving frames per source (output="uint8": both as uint8
+    (B, d, H, W, C) frames, `(255 * out).astype(np.uint8)` channel-last as demo.py:69-71 saves them): the source is encoded
     once (B rows), the field, the embedding, the decoder and the refinement run on the B*d rows v*d + f, and the warps read
     source row v for every frame of video v (the reference's grid_sample over a depth-1 volume, generator.py:51-58)."""
 
@@ -98,6 +99,8 @@ class MotionTransferGenerator(nn.Module):
         if self.training:
             raise RuntimeError("encode_source works in evaluation mode: the appearance encoder's BatchNorm layers would take "
                                "their statistics from this call's batch")
+        if ops.is_u8(source_image):
+            ops.require_inference(self, source_image)
         if source_image.dim() != 5 or source_image.shape[2] != 1:
             raise NotImplementedError("the generator takes one source frame per video; got a source of shape %s"
                                       % (tuple(source_image.shape),))
@@ -118,11 +121,20 @@ class MotionTransferGenerator(nn.Module):
             raise RuntimeError("encode_source: an activation of the state still waits for its norm layer")
         return state
 
-    def forward(self, source_image, kp_driving, kp_source, source_state=None):
+    def forward(self, source_image, kp_driving, kp_source, source_state=None, output="float"):
         """source_state: what encode_source(source_image) returned -- the encoder and the source's layout conversions are skipped
-        (evaluation mode; `source_image` then only gives the shapes).  None: everything is computed here."""
+        (evaluation mode; `source_image` then only gives the shapes).  None: everything is computed here.
+        source_image: (B, C, 1, H, W) fp32 or ops.U8Frames (uint8 channel-last, evaluation mode without gradients).
+        output: "float" -- fp32 (B, C, d, H, W); "uint8" -- uint8 (B, d, H, W, C) written by the last kernels themselves (the fp32
+        tensors are not made); evaluation mode under torch.no_grad() only."""
+        if ops.check_output(output) == "uint8":
+            if self.training or torch.is_grad_enabled():
+                raise RuntimeError('output="uint8" carries no gradient: call .eval() and wrap the call in torch.no_grad() '
+                                   '(or keep output="float")')
+        if ops.is_u8(source_image):
+            ops.require_inference(self, source_image)
         if source_state is not None:
-            return self._forward_from_state(source_image, kp_driving, kp_source, source_state)
+            return self._forward_from_state(source_image, kp_driving, kp_source, source_state, output)
         b = source_image.shape[0]
         d = kp_driving['mean'].shape[1]
         if d < 1 or source_image.shape[2] != 1:
@@ -140,9 +152,9 @@ class MotionTransferGenerator(nn.Module):
             emb, ke = self.kp_embedding_module.forward_act(source_image, kp_driving, kp_source)
         # all warps of this forward as one autograd node: one shared field-gradient buffer (ops.WarpAllFn); the B source
         # rows are shared by the d frames of their video, the outputs have B*d rows
-        return self._decode(b, field, emb, ke, mode, skips, src_act)
+        return self._decode(b, field, emb, ke, mode, skips, src_act, output)
 
-    def _forward_from_state(self, source_image, kp_driving, kp_source, state):
+    def _forward_from_state(self, source_image, kp_driving, kp_source, state, output="float"):
         if self.training:
             raise RuntimeError("a source state serves evaluation mode only: in training mode the appearance encoder's BatchNorm "
                                "layers take their statistics from the batch, so the encoder has to run")
@@ -161,14 +173,15 @@ class MotionTransferGenerator(nn.Module):
         emb, ke = None, 0
         if self.kp_embedding_module is not None:
             emb, ke = self.kp_embedding_module.forward_act(source_image, kp_driving, kp_source, src_act=state.emb_src)
-        return self._decode(b, field, emb, ke, mode, state.skips, state.src_act)
+        return self._decode(b, field, emb, ke, mode, state.skips, state.src_act, output)
 
-    def _decode(self, b, field, emb, ke, mode, skips, src_act):
+    def _decode(self, b, field, emb, ke, mode, skips, src_act, output="float"):
         specs = tuple((c, ke) for _, c in skips) + ((self.num_channels, 0),)
         outs = ops.WarpAllFn.apply(field, emb, mode, specs, *([a for a, _ in skips] + [src_act]))
         warped = [(o, c + ke) for o, (_, c) in zip(outs[:-1], skips)]
         deformed_img = outs[-1]
-        video_deformed = ops.from_act(deformed_img, self.num_channels, b)
+        u8 = output == "uint8"
+        video_deformed = ops.act_to_u8(deformed_img, self.num_channels, b) if u8 else ops.from_act(deformed_img, self.num_channels, b)
         out, c = self.video_decoder.forward_act(warped)
         last, sums = None, None
         blocks = list(self.refinement_module.named_children())
@@ -180,5 +193,8 @@ class MotionTransferGenerator(nn.Module):
                 res = block.forward_act(out, c, x_sums=sums, want_stats=more)
                 out, c = res[0], res[1]
                 sums = res[2] if more else None
-        video_prediction = ops.Conv1x1SigmoidFn.apply(out, last.weight, last.bias, c, b)
+        if u8:
+            video_prediction = ops.conv1x1_sigmoid_u8(out, last.weight, last.bias, c, b)
+        else:
+            video_prediction = ops.Conv1x1SigmoidFn.apply(out, last.weight, last.bias, c, b)
         return {"video_prediction": video_prediction, "video_deformed": video_deformed}

@@ -77,6 +77,10 @@ class KPDetector(nn.Module):
         self._last_heat = None
 
     def forward(self, x):
+        """x: (B,C,D,H,W) fp32, or ops.U8Frames -- uint8 channel-last frames, converted straight into the kernels' layout
+        (evaluation mode, no gradient)"""
+        if ops.is_u8(x):
+            ops.require_inference(self, x)
         b, _, d = x.shape[:3]
         act = ops.to_act(x, ops.step_from_scale(self.scale_factor))
         heat, k = self.predictor.forward_act(act, self.num_channels)

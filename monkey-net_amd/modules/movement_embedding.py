@@ -36,6 +36,8 @@ class MovementEmbeddingModule(nn.Module):
         d, k = kp_driving['mean'].shape[1:3]
         img = None
         if self.use_deformed_source_image:
+            if src_act is None and ops.is_u8(source_image):          # uint8 frames: straight to the act, inference only
+                ops.require_inference(self, source_image)
             img = src_act if src_act is not None else ops.to_act(source_image, step)
         var_d, const_var = _split_variance(kp_driving, self.kp_variance) if self.use_heatmap else (None, 1.0)
         var_s, _ = _split_variance(kp_source, self.kp_variance) if self.use_heatmap else (None, 1.0)
