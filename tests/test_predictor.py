@@ -89,10 +89,15 @@ def _loss(out, seed):
 
 # ---- kernels ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("transA,transB", [(0, 1), (0, 0), (1, 0), (1, 1)])
-@pytest.mark.parametrize("M,N,K,grouped", [(37, 45, 23, False), (70, 24, 60, True), (40, 24, 1100, False)])
+@pytest.mark.parametrize("M,N,K,grouped", [
+    (37, 45, 23, False), (70, 24, 60, True), (40, 24, 1100, False),
+    (70, 130, 23, False),       # 2 x 3 tiles (blockIdx.y = 1 with n0 = 64, 128), ragged in M and N, K not a multiple of 16
+    (5, 200, 3, False),         # K < 16: one partly filled K step; four N tiles
+    (70, 130, 1540, True),      # three K splits (chunks 528, 528, 484: the last ends inside a 16-wide step) of a grouped K-major
+])                              # operand, on 2 x 3 tiles: the shape of the dW_ih GEMM (K = T * B)
 def test_gemm_against_fp64(be, transA, transB, M, N, K, grouped):
-    """all four operand orientations, grouped rows (a [G, R, C] view read in (r, g) order), split-K (K = 1100 on one tile), bias,
-    an output row pitch wider than N whose pad columns stay untouched"""
+    """all four operand orientations, grouped rows (a [G, R, C] view read in (r, g) order), split-K (K = 1100 on one tile, K = 1540
+    on six), more than one tile in M and N, bias, an output row pitch wider than N whose pad columns stay untouched"""
     torch.manual_seed(M + N + K + 2 * transA + transB)
     A = torch.randn(K, M) if transA else torch.randn(M, K)
     B = torch.randn(N, K) if transB else torch.randn(K, N)
@@ -113,6 +118,8 @@ def test_gemm_against_fp64(be, transA, transB, M, N, K, grouped):
     ws_n = be.query("mnk_gru_gemm_workspace_floats", M, N, K)
     if K == 1100:
         assert ws_n > 0
+    if K == 1540:
+        assert ws_n == 3 * M * N
     ws = be.empty(max(ws_n, 1))
     be.call("mnk_gru_gemm", transA, transB, M, N, K, a, lda, ag, ldag, b, ldb, bg, ldbg, be.t(bias), C, ldc, ws, ws_n)
     be.sync()
@@ -169,20 +176,23 @@ def test_step_fwd_against_fp64(be, B, H, gemv):
     assert (gates.double() - gref).abs().max() < 2e-5 * max(1.0, float(gref.abs().max()))
 
 
-@pytest.mark.parametrize("B,H", [(1, 40), (5, 72), (33, 40)])
-def test_step_bwd_against_fp64(be, B, H):
-    """gates backward of the last step, then one fused step backward (dh_{t-1} + the gate backward of step t - 1) and the final
-    dh0 form, against float64 autograd of two GRU steps"""
+def _two_step_bwd_case(B, H, dtype=torch.float64, w_scale=0.3):
+    """Two chained GRU steps h0 -> h1 -> h2 with L = <h1, dy0> + <h2, dy1 + dhn>, computed with autograd in `dtype` (the inputs
+    are drawn in float32, so every dtype sees the same values).  Returns a namespace of the inputs (w_hh, b_hh, h0, gi0, gi1,
+    dy0, dy1, dhn), the forward values the kernels are handed (h1, the saved gates g0, g1 = r | z | n | hn) and the gradients:
+    dgi_t = dL/d(gi_t), dgh_t = dL/d(h_{t-1} W_hh^T + b_hh), dh1 = dL/dh_1 (dy0 included), dh0 = dL/dh_0, and last(dh): the
+    last step's (dgi1, dgh1, carry) for dL/dh_2 = dh alone (one term of dy1 + dhn)."""
+    from types import SimpleNamespace
     torch.manual_seed(B + H)
-    w_hh = (torch.randn(3 * H, H) * 0.3).double()
-    b_hh = (torch.randn(3 * H) * 0.2).double()
-    h0 = torch.randn(B, H).double().requires_grad_()
-    gi0, gi1 = torch.randn(B, 3 * H).double(), torch.randn(B, 3 * H).double()
+    w_hh = (torch.randn(3 * H, H) * w_scale).to(dtype)
+    b_hh = (torch.randn(3 * H) * 0.2).to(dtype)
+    h0 = torch.randn(B, H).to(dtype).requires_grad_()
+    gi0, gi1 = torch.randn(B, 3 * H).to(dtype), torch.randn(B, 3 * H).to(dtype)
     h1, g0 = _step_ref(h0, w_hh, b_hh, gi0)
     h1.retain_grad()
     h2, g1 = _step_ref(h1, w_hh, b_hh, gi1)
-    dy1, dy0 = torch.randn(B, H).double(), torch.randn(B, H).double()
-    dhn = torch.randn(B, H).double()
+    dy1, dy0 = torch.randn(B, H).to(dtype), torch.randn(B, H).to(dtype)
+    dhn = torch.randn(B, H).to(dtype)
     # gradients of the pre-activations: dGi_t = d(gi_t), dGh_t = d(h_{t-1} W_hh^T + b_hh)
     gi0.requires_grad_(), gi1.requires_grad_()
     gh0 = (h0 @ w_hh.t() + b_hh).detach().requires_grad_()
@@ -199,9 +209,23 @@ def test_step_bwd_against_fp64(be, B, H):
     L.backward()
     dh1 = h1c.grad + gh1.grad @ w_hh + dy0       # dL/dh_1, the output's gradient at t = 0 included
     (cell(h0, gi0, gh0) * dh1).sum().backward()
-    dgi1_ref, dgh1_ref = gi1.grad, gh1.grad
-    dgi0_ref, dgh0_ref = gi0.grad, gh0.grad
-    dh0_ref = gh0.grad @ w_hh + h0.grad
+
+    def last(dh):
+        a, b = gi1.detach().requires_grad_(), gh1.detach().requires_grad_()
+        da, db = torch.autograd.grad((cell(h1c.detach(), a, b) * dh).sum(), (a, b))
+        return da, db, dh * g1.detach()[:, H:2 * H]
+    return SimpleNamespace(w_hh=w_hh, b_hh=b_hh, h0=h0, h1=h1, gi0=gi0, gi1=gi1, g0=g0, g1=g1, dy0=dy0, dy1=dy1, dhn=dhn,
+                           dgi1=gi1.grad, dgh1=gh1.grad, dgi0=gi0.grad, dgh0=gh0.grad, dh1=dh1.detach(),
+                           dh0=gh0.grad @ w_hh + h0.grad, last=last)
+
+
+@pytest.mark.parametrize("B,H", [(1, 40), (5, 72), (33, 40)])
+def test_step_bwd_against_fp64(be, B, H):
+    """gates backward of the last step, then one fused step backward (dh_{t-1} + the gate backward of step t - 1) and the final
+    dh0 form, against float64 autograd of two GRU steps"""
+    c = _two_step_bwd_case(B, H)
+    w_hh, h0, h1, g0, g1, dy0, dy1, dhn = c.w_hh, c.h0, c.h1, c.g0, c.g1, c.dy0, c.dy1, c.dhn
+    dgi1_ref, dgh1_ref, dgi0_ref, dgh0_ref, dh0_ref = c.dgi1, c.dgh1, c.dgi0, c.dgh0, c.dh0
 
     f = lambda t: be.t(t.detach().float())
     gates0, gates1 = f(g0), f(g1)
@@ -306,6 +330,7 @@ def _module_case(be, B, T, num_kp, matrix, H, num_layers=1, with_h0=False, seed=
     (3, 1, 10, False, 72, True),        # I = 20, float kp_variance (no 'var' key), one step, h0 given
     (5, 5, 4, True, 72, True),          # I = 24 (shapes.yaml), the MFMA tile form of the step
     (5, 5, 10, False, 40, False),
+    (33, 3, 4, True, 132, True),        # two batch tiles, five hidden tiles / K chunks; N = cols = 396 in the GEMMs / column sums
 ])
 def test_module_forward_and_gradients_against_fp64(be, B, T, num_kp, matrix, H, with_h0):
     _module_case(be, B, T, num_kp, matrix, H, with_h0=with_h0, seed=B * 7 + T)
