@@ -12,6 +12,7 @@ Two things outlive a call here that mnk.engine.Transfer computes per call:
 import torch
 
 from . import _lib
+from . import graphs as mgraphs
 from . import ops as mops
 
 
@@ -187,10 +188,6 @@ class AnimationSession:
         return {"video_prediction": out["video_prediction"], "video_deformed": out["video_deformed"],
                 "kp_driving": kp_driving, "kp_source": self._kp_source, "kp_norm": kp_norm}
 
-    def _fingerprint(self):
-        """what a frozen-weight program depends on (mnk.dropin.EvalRunner._fingerprint, over both networks)"""
-        return (mops._PACK_EPOCH[0], mops._BN_EVAL_EPOCH[0], tuple((t._version, t.data_ptr()) for t in self._weights))
-
     def _capture(self, frames, fp):
         """one linear hipGraph for this push shape, with frozen weights.  The warm-up pushes run the real launches, the anchoring
         one included: the anchor and its flag are put back afterwards, so the program starts from the state the session was in.
@@ -201,25 +198,10 @@ class AnimationSession:
         snap = self.anchor.snapshot()
         if self._cap is None:
             self._cap = torch.cuda.Stream()
-        cap = self._cap
-        cap.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(cap):
-            for _ in range(2):
-                self._forward(static_in)
-        torch.cuda.current_stream().wait_stream(cap)
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        mops.FROZEN_CAPTURE[0] = True
-        try:
-            with torch.cuda.graph(graph, stream=cap):
-                static_out = self._forward(static_in)
-        finally:
-            mops.FROZEN_CAPTURE[0] = False
+        mgraphs.warm_up(lambda: self._forward(static_in), 2, stream=self._cap)
+        graph, static_out = mgraphs.capture(lambda: self._forward(static_in), stream=self._cap, frozen=True)
         self.anchor.restore(snap)
-        # the graph reads the cached norm coefficients by address; that cache keeps one entry per layer (an eager call on another
-        # stream replaces it): the program holds what it reads
-        coeffs = [mops._BN_EVAL.get(id(b)) for m in (self.kp_detector, self.generator) for b in m.buffers()]
-        return graph, static_in, static_out, fp, coeffs
+        return graph, static_in, static_out, fp, mops.held_eval_coeffs((self.kp_detector, self.generator))
 
     def push(self, frames):
         if self._state is None:
@@ -238,7 +220,7 @@ class AnimationSession:
                 # (B, n) for float frames in and out, as ever; other input / output kinds append theirs: (B, n, kind, output)
                 kinds = (mops.frame_kind(frames), self.output)
                 key = (b, n) if kinds == (("float", c), "float") else (b, n) + kinds
-                prog, fp = self._programs.get(key), self._fingerprint()
+                prog, fp = self._programs.get(key), mops.weights_fingerprint(self._weights)
                 if prog is None or prog[3] != fp:
                     prog = self._programs[key] = self._capture(frames, fp)
                 graph, static_in, out = prog[:3]

@@ -12,7 +12,7 @@ Every statement of that loop is Python that launches a few hundred small kernels
 host (14.3 ms per iteration where the captured iteration of TrainStep takes 10.3).  sync_batchnorm.DataParallelWithCallback
 recognises the two wrapped modules (attributes kp_extractor / generator / discriminator / train_params) and hands their calls
 to ONE TrainPairRunner per network triple, which splits the iteration into three phases, each captured once as a hipGraph
-(one memory pool, the make_graphed_callables pattern with the library's own capture):
+(one memory pool, the make_graphed_callables pattern with the library's own capture, mnk.graphs.Segments):
 
   A  forward: key-point detector on [source | driving], generator, ONE discriminator pass on [generated; real] that serves the
      generator loss AND the discriminator loss (the reference's second discriminator forward recomputes the first one's values:
@@ -38,13 +38,13 @@ launches (what the CPU-emulator tests exercise; also the form used when the devi
 Returned tensors of the graph form (loss vectors, `generated`, `kp_joined`) are static buffers that the next
 generator_full_par(x) call overwrites -- the loop's `.cpu()` copies and logger calls read them before that.
 """
-import gc
 import warnings
 import weakref
 
 import torch
 
 from . import dist as mdist
+from . import graphs as mgraphs
 from . import knobs
 from . import ops as mops
 
@@ -219,77 +219,43 @@ class TrainPairRunner:
         prog.x = {k: x[k].to(dev).clone() for k in ("source", "video")}
         mods = (self.kp, self.gen, self.disc)
         snap = [(t, t.detach().clone()) for m in mods for t in m.buffers()]       # BatchNorm running statistics
-        n_g = None
+
+        def iteration():                 # sizes scratch buffers, creates the packed weights and every descriptor table
+            st = self._phase_a(prog.x)
+            prog.g_grads = [torch.full((b,), 1.0 / b, device=dev) for _ in st["g_vec"]]     # (the last run's stay the program's)
+            prog.d_grads = [torch.full((b,), 1.0 / b, device=dev) for _ in st["d_vec"]]
+            self._phase_b(st, prog.g_grads)
+            self._phase_c(st, prog.d_grads)
+            del st
+            self._clear_grads()
+
         side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
         try:
-            with torch.cuda.stream(side):
-                for it in range(2):      # sizes scratch buffers, creates the packed weights and every descriptor table
-                    st = self._phase_a(prog.x)
-                    n_g, n_d = len(st["g_vec"]), len(st["d_vec"])
-                    ones_g = [torch.full((b,), 1.0 / b, device=dev) for _ in range(n_g)]
-                    ones_d = [torch.full((b,), 1.0 / b, device=dev) for _ in range(n_d)]
-                    self._phase_b(st, ones_g)
-                    self._phase_c(st, ones_d)
-                    del st
-                    self._clear_grads()
-                prog.g_grads = [torch.full((b,), 1.0 / b, device=dev) for _ in range(n_g)]
-                prog.d_grads = [torch.full((b,), 1.0 / b, device=dev) for _ in range(n_d)]
-                mops.repack_registered()     # every packed layout fresh: no pack launch is recorded into phase A
-        except Exception as e:           # (no capture has begun: nothing is left half-recorded)
+            mgraphs.warm_up(iteration, 2, side)
+            mgraphs.warm_up(mops.repack_registered, 1, side)     # every packed layout fresh: no pack launch is recorded into phase A
+        except Exception as e:           # (no capture has begun: nothing is left half-recorded; the side stream is joined back)
             warnings.warn("mnk.dropin: the warm-up before the capture failed (%s: %s); the wrapped modules run as they are"
                           % (type(e).__name__, e))
             return None
         finally:
-            torch.cuda.current_stream().wait_stream(side)
-            st = None                    # (the autograd graph of a failed warm-up iteration)
-            self._clear_grads()
+            self._clear_grads()          # (the autograd graph of a failed warm-up iteration went with its frame)
             mops.clear_dz_stats()
             with torch.no_grad():
                 for t, c in snap:
                     t.copy_(c)
-        torch.cuda.synchronize()
-        gc.collect()
-        torch.cuda.empty_cache()
-        gc_was_on = gc.isenabled()
-        gc.disable()
-        pool = torch.cuda.graph_pool_handle()
+        mgraphs.settle()
         cap = torch.cuda.Stream()
         cap.wait_stream(torch.cuda.current_stream())
-        graphs = []
-        current = [None]
-
-        def captured(fn):
-            g = torch.cuda.CUDAGraph()
-            g.capture_begin(pool=pool)
-            current[0] = g
-            fn()
-            g.capture_end()
-            current[0] = None
-            graphs.append(g)
-            return g
-
         state = {}
-        try:
-            with torch.cuda.stream(cap):
-                prog.gA = captured(lambda: state.update(self._phase_a(prog.x)))
-                prog.gB = captured(lambda: self._phase_b(state, prog.g_grads))
-                prog.grads_g = [(p, self.owners[n].sink(p)) for n, ps in (("g", self.g_params), ("k", self.k_params))
-                                for p in ps if p.grad is not None]
-                for p, _ in prog.grads_g:
-                    p.grad = None
-                prog.gC = captured(lambda: self._phase_c(state, prog.d_grads))
-                prog.grads_d = [(p, self.owners["d"].sink(p)) for p in self.d_params if p.grad is not None]
-        except BaseException:
-            if current[0] is not None:
-                try:
-                    current[0].capture_end()
-                except Exception:
-                    _BROKEN.append(current[0])        # (its destructor would abort the process: keep it)
-            raise
-        finally:
-            if gc_was_on:
-                gc.enable()
+        with mgraphs.Segments() as seg, torch.cuda.stream(cap):
+            prog.gA = seg.captured(lambda: state.update(self._phase_a(prog.x)))
+            prog.gB = seg.captured(lambda: self._phase_b(state, prog.g_grads))
+            prog.grads_g = [(p, self.owners[n].sink(p)) for n, ps in (("g", self.g_params), ("k", self.k_params))
+                            for p in ps if p.grad is not None]
+            for p, _ in prog.grads_g:
+                p.grad = None
+            prog.gC = seg.captured(lambda: self._phase_c(state, prog.d_grads))
+            prog.grads_d = [(p, self.owners["d"].sink(p)) for p in self.d_params if p.grad is not None]
         torch.cuda.current_stream().wait_stream(cap)
         prog.g_vec = [v.detach() for v in state["g_vec"]]
         prog.d_vec = [v.detach() for v in state["d_vec"]]
@@ -417,7 +383,6 @@ def train_precision():
     return scope if scope != "fp32" else mops.check_precision(knobs.get("MNK_TRAIN_PRECISION"))
 
 
-_BROKEN = []
 _RUNNERS = {}
 
 
@@ -495,11 +460,6 @@ class EvalRunner:
             return type(obj)(EvalRunner._rebuild(v, leaves, path + (i,)) for i, v in enumerate(obj))
         return obj
 
-    def _fingerprint(self, module):
-        # (data_ptr: `p.data = ...`, module.float() / .to() swap the storage the graph reads and keep _version)
-        return (mops._PACK_EPOCH[0], mops._BN_EVAL_EPOCH[0], tuple((p._version, p.data_ptr()) for p in module.parameters()),
-                tuple((b._version, b.data_ptr()) for b in module.buffers()))
-
     def __call__(self, inputs, kwargs, device):
         module = self._module()
         flat = []
@@ -508,7 +468,7 @@ class EvalRunner:
             return NotImplemented
         opts = eval_options()
         key = (opts, key)
-        fp = self._fingerprint(module)
+        fp = mops.weights_fingerprint((*module.parameters(), *module.buffers()))
         prog = self.programs.get(key)
         if prog is None or prog["fp"] != fp:
             if len(self.programs) >= self.MAX_PROGRAMS:
@@ -556,25 +516,13 @@ class EvalRunner:
         leaves = {path: s for (path, _), s in zip(flat, static)}
         s_in, s_kw = self._rebuild((inputs, kwargs), leaves)
         cap = torch.cuda.Stream()
-        cap.wait_stream(torch.cuda.current_stream())
-        # (the caches are keyed by stream: fill them on the stream the capture runs on)
-        with torch.cuda.stream(cap), mops.eval_options(*opts):
-            for _ in range(2):
-                module(*s_in, **s_kw)
-        torch.cuda.current_stream().wait_stream(cap)
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        mops.FROZEN_CAPTURE[0] = True
-        try:
-            with torch.cuda.graph(graph, stream=cap), mops.eval_options(*opts):
-                out = module(*s_in, **s_kw)
-        finally:
-            mops.FROZEN_CAPTURE[0] = False
+        with mops.eval_options(*opts):
+            # (the caches are keyed by stream: fill them on the stream the capture runs on)
+            mgraphs.warm_up(lambda: module(*s_in, **s_kw), 2, stream=cap)
+            graph, out = mgraphs.capture(lambda: module(*s_in, **s_kw), stream=cap, frozen=True)
         self.stats["captures"] += 1
-        # the graph reads the cached evaluation-mode norm coefficients by address, and that cache keeps ONE entry per layer, keyed by
-        # the stream among others: the warm-up of the next program (a stream of its own) replaces it.  The program holds what it reads
-        coeffs = [mops._BN_EVAL.get(id(b)) for b in module.buffers()]
-        return {"graph": graph, "static": static, "out": out, "fp": fp, "coeffs": coeffs}
+        # (the warm-up of the next program, on a stream of its own, replaces the norm coefficients this graph reads by address)
+        return {"graph": graph, "static": static, "out": out, "fp": fp, "coeffs": mops.held_eval_coeffs((module,))}
 
 
 def _clone_all(obj):

@@ -6,6 +6,7 @@ import torch
 
 from modules.losses import generator_loss, discriminator_loss
 from . import dist as mdist
+from . import graphs as mgraphs
 from . import knobs
 from . import ops as mops
 
@@ -128,9 +129,6 @@ class DiscriminatorFullModel(torch.nn.Module):
                                   loss_weights=self.train_params['loss_weights'])
 
 
-_BROKEN_CAPTURES = []
-
-
 class TrainStep:
     """One iteration of train.py:110-136 on this rank's shard, with gradients averaged over ranks (RCCL) before
     every optimiser step."""
@@ -151,7 +149,7 @@ class TrainStep:
         self.precision = mops.check_precision(precision)
         self.mnk_adam = True if fused_adam is None else bool(fused_adam)
         self._graph = None                    # the captured iteration: a list of hipGraphs and host calls between them
-        self._segment = None                  # (graph being captured, pool) while _capture runs
+        self._segments = None                 # the mnk.graphs.Segments being captured while _capture runs
         self._ones = {}
         self._replaying = False               # inside step()'s replay of a captured iteration (host calls look at it)
         self._static_x = None
@@ -238,83 +236,50 @@ class TrainStep:
             "graph capture with torch.distributed active was disabled (MNK_DIST_GRAPH=0)"
         self._static_x = {k: v.clone() for k, v in x.items()}
         snap = self._snapshot()
-        import gc
+        iteration = lambda: self._eager_step(self._static_x, set_to_none=True)
         side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for it in range(warmup + 1):     # sizes the scratch buffers, creates Adam state and the descriptor tables
-                if it == warmup:
-                    # the captured iteration of one process: the optimiser kernels read the gradients of the deep levels from
-                    # the tap-major partials themselves (MnkAdam.tap_direct; p.grad is not observable inside a replay)
-                    direct = self.mnk_adam and not mdist.grads_active()
-                    for o in (self.opt_g, self.opt_d, self.opt_k):
-                        if hasattr(o, "tap_direct"):
-                            o.tap_direct = bool(direct)
-                    # what torch.cuda.graph() does before a capture -- but in front of the LAST warm-up iteration: objects
-                    # of earlier runs that only the cycle collector frees (models, optimisers) take their packed-weight
-                    # registrations with them, and the tables the capture must find unchanged are keyed by that registry
-                    torch.cuda.synchronize()
-                    gc.collect()
-                    torch.cuda.empty_cache()
-                self._eager_step(self._static_x, set_to_none=True)
-        torch.cuda.current_stream().wait_stream(side)
+        mgraphs.warm_up(iteration, warmup, side)      # sizes the scratch buffers, creates Adam state and the descriptor tables
+        # the captured iteration of one process: the optimiser kernels read the gradients of the deep levels from
+        # the tap-major partials themselves (MnkAdam.tap_direct; p.grad is not observable inside a replay)
+        direct = self.mnk_adam and not mdist.grads_active()
+        for o in (self.opt_g, self.opt_d, self.opt_k):
+            if hasattr(o, "tap_direct"):
+                o.tap_direct = bool(direct)
+        # what torch's graph context does before a capture -- but in front of the LAST warm-up iteration: objects
+        # of earlier runs that only the cycle collector frees (models, optimisers) take their packed-weight
+        # registrations with them, and the tables the capture must find unchanged are keyed by that registry
+        mgraphs.settle()
+        mgraphs.warm_up(iteration, 1, side)
         # The iteration is captured as LINEAR hipGraphs.  A captured graph with a second branch that holds a kernel replays
         # 0.85-1.0 ms slower on this runtime, whatever the branch does (profiles/r03_knob_ab_log.txt), so the overlapped
         # gradient exchange of several ranks is not a branch of one graph: _cut() ends the graph in front of it, the
         # exchange is started / awaited by ordinary stream calls at replay time, and a new graph continues behind it.
         torch.cuda.synchronize()
-        gc_was_on = gc.isenabled()
-        gc.disable()                          # (no collection -- no finaliser -- in the middle of the capture either)
-        program = []
-        pool = torch.cuda.graph_pool_handle()
         cap = torch.cuda.Stream()
         cap.wait_stream(torch.cuda.current_stream())
         try:
-            with torch.cuda.stream(cap):
-                self._segment = [None, pool, program]
-                self._segment_begin()
+            with mgraphs.Segments() as seg, torch.cuda.stream(cap):
+                self._segments = seg
+                seg.begin()
                 self._static_out = self._eager_step(self._static_x, set_to_none=True)
-                if self._segment[0] is not None:
-                    self._segment_end()
-        except BaseException:
-            if self._segment[0] is not None:          # leave the stream out of capture mode, whatever went wrong
-                try:
-                    self._segment[0].capture_end()
-                except Exception:
-                    _BROKEN_CAPTURES.append(self._segment[0])     # (its destructor would abort the process: keep it)
-            raise
+                if seg.open is not None:
+                    seg.end()
         finally:
-            self._segment = None
-            if gc_was_on:
-                gc.enable()
+            self._segments = None
             for o in (self.opt_g, self.opt_d, self.opt_k):      # eager iterations keep every p.grad valid
                 if hasattr(o, "tap_direct"):
                     o.tap_direct = False
         torch.cuda.current_stream().wait_stream(cap)
-        self._graph = program
+        self._graph = seg.pieces
         self._restore(snap)
-
-    def _segment_begin(self):
-        g = torch.cuda.CUDAGraph()
-        g.capture_begin(pool=self._segment[1])
-        self._segment[0] = g
-
-    def _segment_end(self):
-        g, self._segment[0] = self._segment[0], None
-        g.capture_end()
-        self._segment[2].append(g)
 
     def _cut(self, host_call, last=False):
         """`host_call()` now -- and, when the iteration is being captured, between two hipGraphs at every replay (last: nothing
         that launches follows in this iteration, no further graph is begun)."""
-        if self._segment is None:
+        if self._segments is None:
             host_call()
-            return
-        self._segment_end()
-        self._segment[2].append(host_call)
-        host_call()
-        if not last:
-            self._segment_begin()
+        else:
+            self._segments.cut(host_call, last)
 
     def _snapshot(self):
         """Everything the warm-up iterations of the capture change: parameters, buffers (BatchNorm running statistics),
@@ -604,16 +569,8 @@ class Reconstructor:
             # replay always runs on the live parameters: optimiser steps, load_state_dict and in-place writes need no
             # re-capture
             self._static_in = tuple(mops.as_frames(t, device).clone() for t in (source, driving))
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(2):
-                    self._forward(*self._static_in)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            self._graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._graph):
-                self._static_out = self._forward(*self._static_in)
+            mgraphs.warm_up(lambda: self._forward(*self._static_in), 2)
+            self._graph, self._static_out = mgraphs.capture(lambda: self._forward(*self._static_in))
         self._static_in[0].copy_(source, non_blocking=True)
         self._static_in[1].copy_(driving, non_blocking=True)
         self._graph.replay()

@@ -516,10 +516,22 @@ def subpixel(ups):
     return hit[1]
 
 
-# mnk.dropin.EvalRunner captures an evaluation forward with FROZEN weights: the cached packed weights / evaluation-mode norm
-# coefficients are used (and their addresses recorded) instead of re-made inside the graph; the runner re-captures when a
-# parameter, a buffer or the optimiser epoch changes
+# mnk.dropin.EvalRunner and mnk.animation.AnimationSession capture an evaluation forward with FROZEN weights: the cached packed
+# weights / evaluation-mode norm coefficients are used (and their addresses recorded) instead of re-made inside the graph; they
+# re-capture when weights_fingerprint() changes.  Written by mnk.graphs.frozen_weights() only
 FROZEN_CAPTURE = [False]
+
+
+def weights_fingerprint(tensors):
+    """what a frozen-weight program over `tensors` depends on: the pack and norm-coefficient epochs, and per tensor its version and
+    its address (`p.data = ...`, module.float() / .to() swap the storage the graph reads and keep _version)"""
+    return (_PACK_EPOCH[0], _BN_EVAL_EPOCH[0], tuple((t._version, t.data_ptr()) for t in tensors))
+
+
+def held_eval_coeffs(modules):
+    """the cached evaluation-mode norm coefficients of the modules' layers.  A frozen graph reads them by address and the cache
+    keeps ONE entry per layer (a call on another stream replaces it): a frozen program holds what it reads"""
+    return [_BN_EVAL.get(id(b)) for m in modules for b in m.buffers()]
 
 
 # The entry points of one form of the forward / data-gradient implicit GEMM (csrc/conv3x3.hip): packed size and pack of its
@@ -1097,7 +1109,7 @@ def handover_state():
         "_DY_SUMS (BNActFn.backward -> Conv3x3Fn.backward)": _DY_SUMS[0],
         "_SKIP_PARAM_GRADS (no_param_grads)": _SKIP_PARAM_GRADS[0],
         "_SKIP_LEAF_INPUT_GRADS (no_leaf_input_grads)": _SKIP_LEAF_INPUT_GRADS[0],
-        "FROZEN_CAPTURE (mnk.dropin.EvalRunner._capture)": FROZEN_CAPTURE[0],
+        "FROZEN_CAPTURE (mnk.graphs.frozen_weights)": FROZEN_CAPTURE[0],
     }
     return {k: v for k, v in slots.items() if v}
 

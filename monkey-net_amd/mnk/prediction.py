@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import graphs as mgraphs
 from . import gru as mgru
 from . import ops as mops
 from .ops import _p
@@ -314,17 +315,9 @@ class Prediction:
         """the iteration as ONE hipGraph on one stream: a warm-up iteration (it builds the optimiser's descriptor table), the
         capture, then parameters, optimiser state and accumulators put back, so that every replay applies exactly one update"""
         snap = self._snapshot()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            self._iteration(plan, plan.starts)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            self._iteration(plan, plan.starts)
+        mgraphs.warm_up(lambda: self._iteration(plan, plan.starts), 1)
+        plan.graph, _ = mgraphs.capture(lambda: self._iteration(plan, plan.starts))
         self._restore(snap)
-        plan.graph = graph
 
     # ---- fit ----------------------------------------------------------------------------------------------------------------
     def draw_starts(self, pool):
