@@ -390,6 +390,37 @@ int mnk_conv3x3_up_dgrad_bnstats_ex(const float* dy, int ld_dy, int Cout, const 
                                     int H, int W, int C, float* ws, size_t ws_floats, float* stats_partial, const float* bn_y,
                                     int ld_bny, const float* bn_mean, const float* bn_invstd, const float* bn_scale,
                                     const float* bn_beta, float slope, int flags, void* stream);
+/* ---- the pair form: the data gradients w.r.t. BOTH sources [x0 | x1] of an up-sampled two-source convolution in one launch ----
+ * The two mnk_conv3x3_up_dgrad launches of such a layer read the same dy with the same rows, K and loader and differ only in
+ * weight pack (wp0 / wp1 = wp_up_dgrad of source 0 / 1), width (C0 / C1) and output (dx0 / dx1).  The pair entries run them as
+ * one grid whose N dimension covers the tiles of both; every source keeps the launch plan it has on its own (tile, split count,
+ * split ranges), so dx0, dx1, the split-K partials and the statistics partials are those of the two single launches bit for bit.
+ * When both plans split K, one reduction sums both sources' partials (each in split order, with its own row / column map).
+ *   mnk_conv3x3_up_dgrad_pair_form: what the pair does at this shape under the current tuning, for sources as this library
+ *       writes them (16-byte aligned, ld = round_up(C, 4)); bn0 / bn1 != 0: source 0 / 1 is asked for statistics.  0 -- it is
+ *       not one launch: the entries return MNK_EINVAL, launch nothing and compute nothing another way (run the two single
+ *       launches); 1 -- one GEMM launch, and a reduction per source that splits; 2 -- one GEMM launch and one reduction.
+ *       One launch needs one kernel for both: plans with the same block tile (64- or 128-row x 64-channel tiles of the 32x32-MFMA
+ *       family), the K x K buffer loader, the same row order (frame- or position-major), fp32 products ("gemm_bf16x3" off; the
+ *       entries take no MNK_CONV_BF16_TRAIN), and the tuning value "dgrad_pair" (default 1; 0: always two launches).
+ *   workspace: `ws` holds source 0's partials, then source 1's -- mnk_conv3x3_up_dgrad_pair_workspace_floats = the sum of the two
+ *       mnk_conv3x3_up_dgrad_workspace_floats.
+ *   statistics (the _bnstats entry; stats0 / stats1 NULL: that source has no norm-layer record and its bn_* are ignored): each
+ *       buffer is what mnk_conv3x3_up_dgrad_bnstats leaves for that source, mnk_conv3x3_up_dgrad_stats_floats(N, H, W, Cout, C0
+ *       resp. C1) floats; mnk_conv3x3_up_dgrad_pair_stats_floats is their sum. */
+int mnk_conv3x3_up_dgrad_pair_form(int N, int H, int W, int Cout, int C0, int C1, int bn0, int bn1);
+size_t mnk_conv3x3_up_dgrad_pair_workspace_floats(int N, int H, int W, int Cout, int C0, int C1);
+size_t mnk_conv3x3_up_dgrad_pair_stats_floats(int N, int H, int W, int Cout, int C0, int C1);
+int mnk_conv3x3_up_dgrad_pair(const float* dy, int ld_dy, int Cout, const float* wp0, const float* wp1, float* dx0, int ld_dx0,
+                              float* dx1, int ld_dx1, int N, int H, int W, int C0, int C1, float* ws, size_t ws_floats,
+                              void* stream);
+int mnk_conv3x3_up_dgrad_pair_bnstats(const float* dy, int ld_dy, int Cout, const float* wp0, const float* wp1, float* dx0,
+                                      int ld_dx0, float* dx1, int ld_dx1, int N, int H, int W, int C0, int C1, float* ws,
+                                      size_t ws_floats, float* stats0, const float* bn_y0, int ld_bny0, const float* bn_mean0,
+                                      const float* bn_invstd0, const float* bn_scale0, const float* bn_beta0, float slope0,
+                                      float* stats1, const float* bn_y1, int ld_bny1, const float* bn_mean1,
+                                      const float* bn_invstd1, const float* bn_scale1, const float* bn_beta1, float slope1,
+                                      void* stream);
 
 /* ---- general K x K form of the same kernels (stride 1).  Used for the discriminator's nn.Conv3d((1,4,4)) without
  * padding (modules/discriminator.py:17-18; SURVEY.md section 8f row 1, the first "next" component): forward

@@ -67,6 +67,21 @@ struct EvalNorm {
     int ld_z;
 };
 
+// The SECOND output of a pair launch (conv3x3_igemm_kernel<..., PAIR>): two GEMMs that read the same A operand with the same M, K,
+// geometry and loader -- the data gradients of an up-sampled convolution w.r.t. its two sources [previous output | skip] -- in
+// one grid.  Everything a launch's N side owns, with the plan the source has on its own (make_plan): weight pack, output, width
+// and N tiles, split-K partials and split ranges, statistics.  A block takes these in place of ConvArgs' own fields when its
+// N-tile index is past the first output's tiles and then runs the single launch's code: every output element keeps its bits.
+struct ConvOut {
+    const float* wp;
+    float* y;
+    int ld_y, Cout, gn;
+    float* ws;
+    int ldw, splits, ksteps_per_split;
+    float* stats;
+    BnBwdSrc bnb;
+};
+
 struct ConvArgs {
     const float* x0;
     const float* x1;
@@ -112,6 +127,9 @@ struct ConvArgs {
     // ---- evaluation-mode norm layer in the epilogue (the EN = 1 / 2 kernels); window-major launches (EN = 2) -----------------
     EvalNorm en;
     unsigned mulWo, shWo, mulHo, shHo;   // division of a pool-window index by W / 2 and H / 2 (fast_div)
+    // ---- pair launches (the PAIR kernels; up_dgrad_pair_impl decides) -------------------------------------------------------
+    int gn0;           // N tiles of the first output: tile rows [gn0, gridDim.y) of the launch belong to `o1`
+    ConvOut o1;
 };
 
 // GEMM row -> output pixel.  Frame-major (the memory order): m = (fr * H + h) * W + w -- 64 consecutive rows of a small map
@@ -532,8 +550,15 @@ constexpr int LDS_H = 24;     // padded LDS row of the bf16 planes (16 + 8 halve
 // EN: the launch has an EvalNorm -- 1: applied per element (any row map; the buffer-load loaders); 2: with the 2x2 average pool, on
 // window-major rows (row_pixel): the plain 3x3 fast loader, and the epilogue writes the pooled map.  A template parameter, not a
 // test of a.en: the training instantiations (EN = 0) stay the code they were (profiles/eval_norm_fused.txt, section 2)
-template <int BM, int BN, int WM, int WN, int MODE, int GM = 0, bool PM = false, int EN = 0>     // MODE: 0 generic loader, 1 / 2 the 3x3 fast loader (plain / x2 up-sampled)
-__global__ void __launch_bounds__(256, MNK_IGEMM_OCC) conv3x3_igemm_kernel(ConvArgs a) {
+// PAIR: the launch has two outputs (ConvOut): grid y covers the N tiles of both, grid z the larger split count.  A block picks
+// its output once, from its N-tile index (block-uniform), leaves at once when its split is past that output's count, and is
+// then a block of the single launch.  A template parameter like EN: the other instantiations stay the code they were
+template <int BM, int BN, int WM, int WN, int MODE, int GM = 0, bool PM = false, int EN = 0, bool PAIR = false>     // MODE: 0 generic loader, 1 / 2 the 3x3 fast loader (plain / x2 up-sampled)
+__global__ void __launch_bounds__(256, MNK_IGEMM_OCC) conv3x3_igemm_kernel(ConvArgs a_in) {
+    static_assert(!PAIR || (MODE == 3 && GM == 0 && EN == 0), "pair launches: the K x K buffer loader, fp32 products");
+    ConvArgs a_own;                           // PAIR: the block's own view of the launch
+    const ConvArgs& a = PAIR ? a_own : a_in;
+    if constexpr (PAIR) a_own = a_in;
     static_assert(!PM || (MODE != 0 && GM == 0), "position-major rows: buffer-load loaders, fp32 products");
     constexpr bool WIN = EN == 2;
     static_assert(!WIN || (MODE == 1 && !PM), "window-major rows: the plain 3x3 fast loader");
@@ -570,6 +595,22 @@ __global__ void __launch_bounds__(256, MNK_IGEMM_OCC) conv3x3_igemm_kernel(ConvA
     const int wm = wave / WN, wn = wave % WN;
     int bx, by;
     xcd_tile(a.xcd, bx, by);
+    if constexpr (PAIR) {
+        if (by >= a_in.gn0) {                 // block-uniform: a tile of the second output
+            by -= a_in.gn0;
+            a_own.wp = a_in.o1.wp;
+            a_own.y = a_in.o1.y;
+            a_own.ld_y = a_in.o1.ld_y;
+            a_own.Cout = a_in.o1.Cout;
+            a_own.ws = a_in.o1.ws;
+            a_own.ldw = a_in.o1.ldw;
+            a_own.splits = a_in.o1.splits;
+            a_own.ksteps_per_split = a_in.o1.ksteps_per_split;
+            a_own.stats = a_in.o1.stats;
+            a_own.bnb = a_in.o1.bnb;
+        }
+        if ((int)blockIdx.z >= a_own.splits) return;      // grid z is the larger split count of the two
+    }
     // sub-pixel form: the M tiles of phase (pa, pb) are [phase * tiles_per_phase, ...); each phase has its own weights
     // and its own top / left padding (rows i + pa - 1, i + pa of the low-resolution input)
     const int phase = a.phases > 1 ? bx / a.tiles_per_phase : 0;
@@ -1342,19 +1383,18 @@ static RSMap make_rsmap(long rows, int ld) {
     return m;
 }
 
+// (the body of the kernel: block (bix, biy) of the reduction's own grid -- the pair form below runs it for either output)
 template <bool STATS>
-__global__ void __launch_bounds__(256) conv3x3_splitk_reduce_stats_kernel(const float* __restrict__ ws, int splits, long M,
-                                                                          int ldw, const float* __restrict__ bias,
-                                                                          const float* __restrict__ residual, int ld_res,
-                                                                          float* __restrict__ y, int ld_y, int Cout,
-                                                                          int phases, int H, int W, int tx_n, int ty_n,
-                                                                          long rows_per_block, float* __restrict__ stats,
-                                                                          BnBwdSrc bnb = BnBwdSrc{}) {
-    __shared__ float4 red[2][256];
+__device__ __forceinline__ void splitk_reduce_stats_block(float4 (*red)[256], const unsigned bix, const unsigned biy,
+                                                          const float* __restrict__ ws, int splits, long M, int ldw,
+                                                          const float* __restrict__ bias, const float* __restrict__ residual,
+                                                          int ld_res, float* __restrict__ y, int ld_y, int Cout, int phases, int H,
+                                                          int W, int tx_n, int ty_n, long rows_per_block,
+                                                          float* __restrict__ stats, const BnBwdSrc& bnb) {
     const int tx = threadIdx.x % tx_n, ty = threadIdx.x / tx_n;
-    const int q = blockIdx.x * tx_n + tx, nv = ld_y / 4, c = q * 4;
+    const int q = bix * tx_n + tx, nv = ld_y / 4, c = q * 4;
     const long rows = M * phases;
-    const long r0 = (long)blockIdx.y * rows_per_block;
+    const long r0 = (long)biy * rows_per_block;
     long r1 = r0 + rows_per_block;
     if (r1 > rows) r1 = rows;
     float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
@@ -1463,10 +1503,51 @@ __global__ void __launch_bounds__(256) conv3x3_splitk_reduce_stats_kernel(const 
         __syncthreads();
     }
     if (ty == 0 && q < nv) {
-        float* o = stats + (long)blockIdx.y * 2 * ld_y;
+        float* o = stats + (long)biy * 2 * ld_y;
         *reinterpret_cast<float4*>(o + c) = red[0][tx];
         *reinterpret_cast<float4*>(o + ld_y + c) = red[1][tx];
     }
+}
+
+template <bool STATS>
+__global__ void __launch_bounds__(256) conv3x3_splitk_reduce_stats_kernel(const float* __restrict__ ws, int splits, long M,
+                                                                          int ldw, const float* __restrict__ bias,
+                                                                          const float* __restrict__ residual, int ld_res,
+                                                                          float* __restrict__ y, int ld_y, int Cout,
+                                                                          int phases, int H, int W, int tx_n, int ty_n,
+                                                                          long rows_per_block, float* __restrict__ stats,
+                                                                          BnBwdSrc bnb = BnBwdSrc{}) {
+    __shared__ float4 red[2][256];
+    splitk_reduce_stats_block<STATS>(red, blockIdx.x, blockIdx.y, ws, splits, M, ldw, bias, residual, ld_res, y, ld_y, Cout, phases,
+                                     H, W, tx_n, ty_n, rows_per_block, stats, bnb);
+}
+
+// ---- one reduction for the two outputs of a pair launch (conv3x3_igemm_kernel<..., PAIR>) whose plans both split K ------------
+// Block columns [0, s0.col_tiles) sum the first output's partials, the rest the second's; each output keeps the row / column map
+// it has on its own (make_rsmap: thread shape, rows per block, row blocks -- its statistics partials are sums in that map's
+// order), grid y is the larger row-block count and blocks past their output's count leave at once.  A block runs the single
+// reduction's body: the partials are added in split order, every dx element and every statistics partial keeps its bits.
+struct RsOut {
+    const float* ws;
+    int splits, ldw;
+    float* y;
+    int ld_y, Cout, tx_n, ty_n, col_tiles, row_blocks;
+    long rows_per_block;
+    float* stats;      // nullptr: this output leaves no statistics
+    BnBwdSrc bnb;
+};
+__global__ void __launch_bounds__(256) conv3x3_splitk_reduce_pair_kernel(RsOut s0, RsOut s1, long M, int H, int W) {
+    __shared__ float4 red[2][256];
+    const bool second = blockIdx.x >= (unsigned)s0.col_tiles;
+    const unsigned bix = second ? blockIdx.x - (unsigned)s0.col_tiles : blockIdx.x;
+    if (second) s0 = s1;
+    if (blockIdx.y >= (unsigned)s0.row_blocks) return;
+    if (s0.stats)
+        splitk_reduce_stats_block<true>(red, bix, blockIdx.y, s0.ws, s0.splits, M, s0.ldw, nullptr, nullptr, 0, s0.y, s0.ld_y, s0.Cout,
+                                        1, H, W, s0.tx_n, s0.ty_n, s0.rows_per_block, s0.stats, s0.bnb);
+    else
+        splitk_reduce_stats_block<false>(red, bix, blockIdx.y, s0.ws, s0.splits, M, s0.ldw, nullptr, nullptr, 0, s0.y, s0.ld_y, s0.Cout,
+                                         1, H, W, s0.tx_n, s0.ty_n, s0.rows_per_block, s0.stats, s0.bnb);
 }
 
 // ---- weight packing: Wp[row][chunk][tap][16] --------------------------------------------------------------------
@@ -2038,6 +2119,25 @@ static void launch_plan_tile(const Plan& p, int mode, const IgemmLaunch& L, cons
     else launch_tile<128, 32, 4, 1, GM>(mode, L, a);
 }
 
+// the reduction behind ONE split-K launch: sums its partials into y (+ bias, residual) and, with stats_partial, leaves the statistics
+static void launch_splitk_reduce(hipStream_t s, float* ws, int splits, long M, int ldw, const float* bias, const float* residual,
+                                 int ld_res, float* y, int ld_y, int Cout, int phases, int H, int W, float* stats_partial,
+                                 const BnBwdSrc& bnb) {
+    ProfScope prof(K_CONV_REDUCE, s, (double)splits * M * ldw * 4);
+    if (stats_partial) {
+        const RSMap m = make_rsmap(M * phases, ld_y);
+        hipLaunchKernelGGL(conv3x3_splitk_reduce_stats_kernel<true>, dim3(m.col_tiles, m.row_blocks), dim3(256), 0, s, ws, splits, M,
+                           ldw, bias, residual, ld_res, y, ld_y, Cout, phases, H, W, m.tx, m.ty, m.rows_per_block, stats_partial, bnb);
+    } else if (g_reduce_v4 && (size_t)y % 16 == 0 && (size_t)ws % 16 == 0) {
+        const RSMap m = make_rsmap(M * phases, ld_y);
+        hipLaunchKernelGGL(conv3x3_splitk_reduce_stats_kernel<false>, dim3(m.col_tiles, m.row_blocks), dim3(256), 0, s, ws, splits, M,
+                           ldw, bias, residual, ld_res, y, ld_y, Cout, phases, H, W, m.tx, m.ty, m.rows_per_block, (float*)nullptr,
+                           BnBwdSrc{});
+    } else
+        hipLaunchKernelGGL(conv3x3_splitk_reduce_kernel, dim3(grid_for(M * phases * ld_y * 4, 8192)), dim3(256), 0, s, ws, splits, M,
+                           ldw, bias, residual, ld_res, y, ld_y, Cout, phases, H, W);
+}
+
 // general form behind mnk_conv2d_fwd / mnk_conv3x3_up_fwd / mnk_conv3x3_up_dgrad:
 //   phases == 1: Ho x Wo outputs, input pixel of output (h, w), tap (ky, kx) = (h * stride + ky - pad, w * stride + kx - pad)
 //   phases == 4: the sub-pixel form of [nearest x2 -> 3x3 / pad 1] (ConvArgs): kh = kw = 2, pad = 1, (Hi, Wi) = (Ho, Wo) =
@@ -2182,23 +2282,145 @@ static int conv2d_fwd_impl(const float* x0, int ld0, int C0, const float* x1, in
         else if (p.bn == 16 || p.bn == 48 ? g_gemm16_bf16x3 : g_gemm_bf16x3) launch_plan_tile<1>(p, mode, L, a);
         else launch_plan_tile<0>(p, mode, L, a);
     }
-    if (p.splits > 1 && !defer_splitk) {
-        ProfScope prof(K_CONV_REDUCE, s, (double)p.splits * a.M * p.ldw * 4);
-        if (stats_partial) {
-            const RSMap m = make_rsmap(a.M * phases, ld_y);
-            hipLaunchKernelGGL(conv3x3_splitk_reduce_stats_kernel<true>, dim3(m.col_tiles, m.row_blocks), dim3(256), 0, s, ws,
-                               p.splits, a.M, p.ldw, bias, residual, ld_res, y, ld_y, Cout, phases, a.H, a.W, m.tx, m.ty,
-                               m.rows_per_block, stats_partial, a.bnb);
-        } else if (g_reduce_v4 && (size_t)y % 16 == 0 && (size_t)ws % 16 == 0) {
-            const RSMap m = make_rsmap(a.M * phases, ld_y);
-            hipLaunchKernelGGL(conv3x3_splitk_reduce_stats_kernel<false>, dim3(m.col_tiles, m.row_blocks), dim3(256), 0, s, ws,
-                               p.splits, a.M, p.ldw, bias, residual, ld_res, y, ld_y, Cout, phases, a.H, a.W, m.tx, m.ty,
-                               m.rows_per_block, (float*)nullptr);
-        } else
-            hipLaunchKernelGGL(conv3x3_splitk_reduce_kernel, dim3(grid_for(a.M * phases * ld_y * 4, 8192)), dim3(256), 0, s, ws,
-                               p.splits, a.M, p.ldw, bias, residual, ld_res, y, ld_y, Cout, phases, a.H, a.W);
-    }
+    if (p.splits > 1 && !defer_splitk)
+        launch_splitk_reduce(s, ws, p.splits, a.M, p.ldw, bias, residual, ld_res, y, ld_y, Cout, phases, a.H, a.W, stats_partial, a.bnb);
     MNK_LAUNCH_CHECK();
+    return MNK_OK;
+}
+
+// ---- the data gradients of an up-sampled convolution w.r.t. BOTH of its sources [previous output | skip] in one launch ----------
+// Each source's launch is described as conv2d_fwd_impl describes it on its own (4x4 / stride 2 / pad 1 over dy: plan, loader,
+// row order, work); the two are one grid when the kernel can be one instantiation for both.
+static int g_dgrad_pair = tuning_knob("dgrad_pair", &g_dgrad_pair, 1);      // 0: the two launches of the single entries (A/B runs, tests)
+
+struct UpDgradSide {
+    Launch l;
+    int mode;
+    bool pm;
+    double row_taps, alg;
+};
+// bn: the launch is asked for the backward statistics of the norm layer in front.  (H, W): the low resolution
+static UpDgradSide up_dgrad_side(int ld_dy, bool aligned, int Cout, int N, int H, int W, int C, bool bn) {
+    UpDgradSide d;
+    d.l = plan_launch(16, 1, N, H, W, Cout, 0, C);
+    d.mode = loader_mode(true, 0, 4, 4, 1, 2, 1, 2 * W, ld_dy, aligned);
+    const TapGeom tg = {d.l.p.bm, N, H, W, 2 * H, 2 * W, 4, 4, 1, 2, 1};
+    d.pm = plan_taps(d.l.p, d.mode, false, bn && d.l.p.splits == 1, tg, (long)N * 2 * H * 2 * W * ld_dy * 4, &d.row_taps);
+    d.alg = 2.0 * 4.0 * (double)N * H * W * C * 9.0 * Cout;
+    return d;
+}
+// the tiles the pair kernels are instantiated for (up_dgrad_pair_impl): the ones the flagship's thirteen pairs run on
+static bool pair_tile_ok(const Plan& p) { return p.bn == 64 && (p.bm == 64 || p.bm == 128); }
+// 0: two launches; 1: one GEMM launch (+ a reduction per source that splits); 2: one GEMM launch and one reduction.
+// One kernel instantiation must serve both: the same block tile (both in the 32x32-MFMA family), loader, row order, fp32 products
+static int up_dgrad_pair_form(const UpDgradSide& d0, const UpDgradSide& d1, bool bn0, bool bn1, bool reduce_aligned) {
+    if (!g_dgrad_pair || g_gemm_bf16x3) return 0;
+    const Plan &p0 = d0.l.p, &p1 = d1.l.p;
+    if (d0.l.p.gm <= 0 || d1.l.p.gm <= 0 || !pair_tile_ok(p0) || !pair_tile_ok(p1) || p0.bm != p1.bm || p0.bn != p1.bn) return 0;
+    if (d0.mode != 3 || d1.mode != 3 || d0.pm != d1.pm) return 0;
+    if (d0.pm && p0.bm != 64) return 0;       // (the position-major 128-row tile needs 134 registers: not instantiated as a pair)
+    if (p0.splits == 1 || p1.splits == 1) return 1;
+    // the merged reduction is the float4-row kernel: each source must take that kernel on its own
+    return ((bn0 || (g_reduce_v4 && reduce_aligned)) && (bn1 || (g_reduce_v4 && reduce_aligned))) ? 2 : 1;
+}
+
+
+struct UpDgradOut {
+    const float* wp;
+    float* dx;
+    int ld_dx, C;
+    float* stats;
+    const BnBwdSrc* bnb;
+};
+static int up_dgrad_pair_impl(const char* who, const float* dy, int ld_dy, int Cout, const UpDgradOut (&o)[2], int N, int H, int W,
+                              float* ws, size_t ws_floats, void* stream) {
+    MNK_REQUIRE_FOR(who, dy && N > 0 && H > 0 && W > 0 && Cout > 0 && ld_dy % 4 == 0 && ld_dy >= Cout);
+    UpDgradSide d[2];
+    for (int i = 0; i < 2; ++i) {
+        MNK_REQUIRE_FOR(who, o[i].wp && o[i].dx && o[i].C > 0 && o[i].ld_dx % 4 == 0 && o[i].ld_dx >= o[i].C &&
+                                 o[i].ld_dx <= round_up(o[i].C, 16));
+        MNK_REQUIRE_FOR(who, (long)N * H * W < (1L << 31) && (long)N * H * W * round_up(o[i].C, 16) < (1L << 32));
+        MNK_REQUIRE_FOR(who, (o[i].stats != nullptr) == (o[i].bnb != nullptr));
+        d[i] = up_dgrad_side(ld_dy, (size_t)dy % 16 == 0, Cout, N, H, W, o[i].C, o[i].stats != nullptr);
+        const BnBwdSrc* b = o[i].bnb;
+        MNK_REQUIRE_FOR(who, !b || (b->y && b->mean && b->invstd && b->scale && b->beta && b->ld >= o[i].C &&
+                                    o[i].ld_dx == round_up(o[i].C, 4) && d[i].l.stats_floats));
+    }
+    const size_t ws0 = d[0].l.ws_floats, ws1 = d[1].l.ws_floats;       // (multiples of 4 floats: ldw is)
+    float* const wsv[2] = {ws, ws ? ws + ws0 : nullptr};
+    const bool reduce_aligned = (size_t)ws % 16 == 0 && (size_t)o[0].dx % 16 == 0 && (size_t)o[1].dx % 16 == 0;
+    const int form = up_dgrad_pair_form(d[0], d[1], o[0].stats != nullptr, o[1].stats != nullptr, reduce_aligned);
+    if (!form) {
+        set_error("%s: this pair is not one launch at this shape and tuning (mnk_conv3x3_up_dgrad_pair_form answers 0): run the "
+                  "two single launches", who);
+        return MNK_EINVAL;
+    }
+    if (ws0 + ws1 && (!ws || ws_floats < ws0 + ws1)) {
+        set_error("%s: workspace too small (%zu < %zu floats)", who, ws_floats, ws0 + ws1);
+        return MNK_EWORKSPACE;
+    }
+    const Plan &p0 = d[0].l.p, &p1 = d[1].l.p;
+    ConvArgs a{};
+    a.x0 = dy, a.ld0 = ld_dy, a.C0 = Cout, a.C0p = round_up(Cout, 16);
+    a.clean = 1;
+    a.N = N, a.H = H, a.W = W, a.Hi = 2 * H, a.Wi = 2 * W;
+    a.ntaps = 16, a.kw = 4, a.pad = 1, a.stride = 2, a.pad_x = -1;
+    a.M = (long)N * H * W;
+    a.chunks = a.C0p / 16;
+    a.phases = 1, a.tiles_per_phase = p0.gm;
+    a.ksteps = p0.ksteps;
+    a.xcd = g_xcd_remap;
+    fast_div_consts((unsigned)W, &a.mulW, &a.shW);
+    fast_div_consts((unsigned)H, &a.mulH, &a.shH);
+    fast_div_consts((unsigned)N, &a.mulF, &a.shF);
+    fast_div_consts(4u, &a.mulKW, &a.shKW);
+    fast_div_consts((unsigned)(W > 1 ? W / 2 : 1), &a.mulWo, &a.shWo);
+    fast_div_consts((unsigned)(H > 1 ? H / 2 : 1), &a.mulHo, &a.shHo);
+    a.wp = o[0].wp, a.y = o[0].dx, a.ld_y = o[0].ld_dx, a.Cout = o[0].C;
+    a.phase_wstride = (long)o[0].C * 16 * a.C0p;
+    a.ksteps_per_split = p0.ksteps_per_split, a.splits = p0.splits, a.ws = wsv[0], a.ldw = p0.ldw;
+    a.stats = o[0].stats;
+    a.bnb = o[0].bnb ? *o[0].bnb : BnBwdSrc{};
+    a.gn0 = p0.gn;
+    a.o1.wp = o[1].wp, a.o1.y = o[1].dx, a.o1.ld_y = o[1].ld_dx, a.o1.Cout = o[1].C, a.o1.gn = p1.gn;
+    a.o1.ksteps_per_split = p1.ksteps_per_split, a.o1.splits = p1.splits, a.o1.ws = wsv[1], a.o1.ldw = p1.ldw;
+    a.o1.stats = o[1].stats;
+    a.o1.bnb = o[1].bnb ? *o[1].bnb : BnBwdSrc{};
+    hipStream_t s = (hipStream_t)stream;
+    g_last_evalnorm_form = 0;
+    {
+        // ONE launch in the recorder, with the work of both
+        ProfScope prof(K_CONV_FWD, s, d[0].alg + d[1].alg, 2.0 * Cout * (d[0].row_taps * o[0].C + d[1].row_taps * o[1].C));
+        hipEvent_t ev0, ev1;
+        const bool timed = prof.kernel_events(&ev0, &ev1);
+        const IgemmLaunch L = {dim3(p0.gm, p0.gn + p1.gn, p0.splits > p1.splits ? p0.splits : p1.splits), s, timed, ev0, ev1, d[0].pm, 0};
+        if (p0.bm == 128) launch_igemm(conv3x3_igemm_kernel<128, 64, 2, 2, 3, 0, false, 0, true>, L, a);
+        else if (d[0].pm) launch_igemm(conv3x3_igemm_kernel<64, 64, 2, 2, 3, 0, true, 0, true>, L, a);
+        else launch_igemm(conv3x3_igemm_kernel<64, 64, 2, 2, 3, 0, false, 0, true>, L, a);
+    }
+    if (form == 2) {
+        ProfScope prof(K_CONV_REDUCE, s, ((double)p0.splits * p0.ldw + (double)p1.splits * p1.ldw) * a.M * 4);
+        RsOut r[2];
+        for (int i = 0; i < 2; ++i) {
+            const Plan& p = d[i].l.p;
+            const RSMap m = make_rsmap(a.M, o[i].ld_dx);
+            r[i].ws = wsv[i], r[i].splits = p.splits, r[i].ldw = p.ldw, r[i].y = o[i].dx, r[i].ld_y = o[i].ld_dx, r[i].Cout = o[i].C;
+            r[i].tx_n = m.tx, r[i].ty_n = m.ty, r[i].col_tiles = m.col_tiles, r[i].row_blocks = m.row_blocks;
+            r[i].rows_per_block = m.rows_per_block;
+            r[i].stats = o[i].stats;
+            r[i].bnb = o[i].bnb ? *o[i].bnb : BnBwdSrc{};
+        }
+        hipLaunchKernelGGL(conv3x3_splitk_reduce_pair_kernel,
+                           dim3(r[0].col_tiles + r[1].col_tiles, r[0].row_blocks > r[1].row_blocks ? r[0].row_blocks : r[1].row_blocks),
+                           dim3(256), 0, s, r[0], r[1], a.M, H, W);
+    } else {
+        // a source that does not split has no partials to sum; the other keeps the reduction it has on its own
+        for (int i = 0; i < 2; ++i)
+            if (d[i].l.p.splits > 1)
+                launch_splitk_reduce(s, wsv[i], d[i].l.p.splits, a.M, d[i].l.p.ldw, nullptr, nullptr, 0, o[i].dx, o[i].ld_dx, o[i].C, 1, H,
+                                     W, o[i].stats, o[i].bnb ? *o[i].bnb : BnBwdSrc{});
+    }
+    MNK_LAUNCH_CHECK_FOR(who);
     return MNK_OK;
 }
 
@@ -2323,6 +2545,39 @@ int mnk_conv3x3_up_dgrad_bnstats(const float* dy, int ld_dy, int Cout, const flo
                                  float slope, void* stream) {
     return mnk_conv3x3_up_dgrad_bnstats_ex(dy, ld_dy, Cout, wp_up_dgrad, dx, ld_dx, N, H, W, C, ws, ws_floats, stats_partial, bn_y,
                                            ld_bny, bn_mean, bn_invstd, bn_scale, bn_beta, slope, 0, stream);
+}
+
+// ---- the pair form: both sources' data gradients of an up-sampled two-source convolution in one launch ------------------------
+int mnk_conv3x3_up_dgrad_pair_form(int N, int H, int W, int Cout, int C0, int C1, int bn0, int bn1) {
+    if (N <= 0 || H <= 0 || W <= 0 || Cout <= 0 || C0 <= 0 || C1 <= 0) return 0;
+    const int ld_dy = round_up(Cout, 4);
+    const UpDgradSide d0 = up_dgrad_side(ld_dy, true, Cout, N, H, W, C0, bn0 != 0), d1 = up_dgrad_side(ld_dy, true, Cout, N, H, W, C1, bn1 != 0);
+    if ((bn0 && !d0.l.stats_floats) || (bn1 && !d1.l.stats_floats)) return 0;
+    return up_dgrad_pair_form(d0, d1, bn0 != 0, bn1 != 0, true);
+}
+size_t mnk_conv3x3_up_dgrad_pair_workspace_floats(int N, int H, int W, int Cout, int C0, int C1) {
+    return plan_launch(16, 1, N, H, W, Cout, 0, C0).ws_floats + plan_launch(16, 1, N, H, W, Cout, 0, C1).ws_floats;
+}
+size_t mnk_conv3x3_up_dgrad_pair_stats_floats(int N, int H, int W, int Cout, int C0, int C1) {
+    return plan_launch(16, 1, N, H, W, Cout, 0, C0).stats_floats + plan_launch(16, 1, N, H, W, Cout, 0, C1).stats_floats;
+}
+int mnk_conv3x3_up_dgrad_pair(const float* dy, int ld_dy, int Cout, const float* wp0, const float* wp1, float* dx0, int ld_dx0,
+                              float* dx1, int ld_dx1, int N, int H, int W, int C0, int C1, float* ws, size_t ws_floats,
+                              void* stream) {
+    const UpDgradOut o[2] = {{wp0, dx0, ld_dx0, C0, nullptr, nullptr}, {wp1, dx1, ld_dx1, C1, nullptr, nullptr}};
+    return up_dgrad_pair_impl(__func__, dy, ld_dy, Cout, o, N, H, W, ws, ws_floats, stream);
+}
+int mnk_conv3x3_up_dgrad_pair_bnstats(const float* dy, int ld_dy, int Cout, const float* wp0, const float* wp1, float* dx0,
+                                      int ld_dx0, float* dx1, int ld_dx1, int N, int H, int W, int C0, int C1, float* ws,
+                                      size_t ws_floats, float* stats0, const float* bn_y0, int ld_bny0, const float* bn_mean0,
+                                      const float* bn_invstd0, const float* bn_scale0, const float* bn_beta0, float slope0,
+                                      float* stats1, const float* bn_y1, int ld_bny1, const float* bn_mean1,
+                                      const float* bn_invstd1, const float* bn_scale1, const float* bn_beta1, float slope1,
+                                      void* stream) {
+    const BnBwdSrc b0 = bnb_of(bn_y0, ld_bny0, bn_mean0, bn_invstd0, bn_scale0, bn_beta0, slope0),
+                   b1 = bnb_of(bn_y1, ld_bny1, bn_mean1, bn_invstd1, bn_scale1, bn_beta1, slope1);
+    const UpDgradOut o[2] = {{wp0, dx0, ld_dx0, C0, stats0, stats0 ? &b0 : nullptr}, {wp1, dx1, ld_dx1, C1, stats1, stats1 ? &b1 : nullptr}};
+    return up_dgrad_pair_impl(__func__, dy, ld_dy, Cout, o, N, H, W, ws, ws_floats, stream);
 }
 
 // ---- 3x3 / pad 1 forms (the hot path's nn.Conv3d (1,3,3)) ------------------------------------------------------------

@@ -1154,6 +1154,52 @@ def param_grad_request(ctx, edge):
         return GRAD_RETURNED
 
 
+def _dgrad_rec(rec, cc, shape):
+    """the norm-layer record (_BN_OF) a data-gradient launch into a source of `cc` channels keeps, or None: the record must be of
+    that width, and small layers make their backward statistics inside their own one-launch kernel.  shape: what rec.y must look
+    like (None: not checked here)"""
+    if rec is None:
+        return None
+    rows = rec.y.numel() // rec.y.shape[-1]
+    if rec.c != cc or rec.y.shape[-1] != ceil4(cc) or small_bn(rows, True, cc) or _small_sync(rows):
+        return None
+    return rec if shape is None or tuple(rec.y.shape) == shape else None
+
+
+def _up_dgrad_pair(dy, cout, wds, n, h, w, cs, recs):
+    """The data gradients of an up-sampled convolution w.r.t. both of its sources as ONE launch (mnk_conv3x3_up_dgrad_pair: the
+    two GEMMs read the same dy and keep their own plans, so every bit is that of the two single launches) -> [dx0, dx1], with the
+    _DZ_STATS hand-over of each source that has a record; None where the pair is not one launch at this shape and tuning
+    (mnk_conv3x3_up_dgrad_pair_form): the caller issues the two launches.  (n, h, w): the low resolution."""
+    if dy.shape[-1] != ceil4(cout) or dy.data_ptr() % 16:
+        return None
+    if not _query("mnk_conv3x3_up_dgrad_pair_form", n, h, w, cout, cs[0], cs[1], int(recs[0] is not None), int(recs[1] is not None)):
+        return None
+    _drop_stale_split_pending()
+    dxs = [torch.empty(n, h, w, ceil4(c), dtype=torch.float32, device=dy.device) for c in cs]
+    nws = _query("mnk_conv3x3_up_dgrad_pair_workspace_floats", n, h, w, cout, cs[0], cs[1])
+    ws = SCRATCH.get("ws", nws, dy) if nws else None
+    head = (_p(dy), dy.shape[-1], cout, _p(wds[0]), _p(wds[1]), _p(dxs[0]), dxs[0].shape[-1], _p(dxs[1]), dxs[1].shape[-1], n, h, w,
+            cs[0], cs[1], _p(ws), nws)
+    if recs[0] is None and recs[1] is None:
+        _call("mnk_conv3x3_up_dgrad_pair", dy, *head)
+        return dxs
+    sts, tail = [], ()
+    for c, rec in zip(cs, recs):
+        if rec is None:
+            sts.append(None)
+            tail += (None, None, 0, None, None, None, None, -1.0)
+            continue
+        st = torch.empty(_query("mnk_conv3x3_up_dgrad_stats_floats", n, h, w, cout, c), dtype=torch.float32, device=dy.device)
+        sts.append(st)                   # lives until the norm layer reads it
+        tail += (_p(st), _p(rec.y), rec.y.shape[-1], _p(rec.mean), _p(rec.invstd), _p(rec.scale), _p(rec.beta), float(rec.slope))
+    _call("mnk_conv3x3_up_dgrad_pair_bnstats", dy, *head, *tail)
+    for dx, st, rec in zip(dxs, sts, recs):
+        if st is not None:
+            _DZ_STATS[dx.data_ptr()] = (dx, st, st.numel() // (2 * dx.shape[-1]), rec.y.data_ptr(), dx._version)
+    return dxs
+
+
 class Conv3x3Fn(_Fn):
     """nn.Conv3d((1,3,3), padding (0,1,1)) over the channel concatenation [x0 | x1], optionally read through the
     nearest x2 up-sampling (UpBlock3D, modules/util.py:83-85), plus bias and residual add (ResBlock3D :66-67)."""
@@ -1210,16 +1256,23 @@ class Conv3x3Fn(_Fn):
         ld_dy = dy.shape[-1]
         cin = c0 + c1
         grads = [None, None]
+        pair = None
+        if ctx.up and not ctx.bf16 and x1 is not None and c1 and ctx.needs_input_grad[0] and ctx.needs_input_grad[1]:
+            # both sources of an up-sampled convolution: the two data gradients read the same dy -- one launch where the library
+            # can make them one (else None: the loop below)
+            shapes = [(n, h // 2, w // 2, ceil4(cc)) for cc in (c0, c1)]
+            pair = _up_dgrad_pair(dy, cout, ctx.wd, n, h // 2, w // 2, (c0, c1),
+                                  [_dgrad_rec(ctx.src_bn[i], cc, shapes[i]) for i, cc in enumerate((c0, c1))])
         for i, (src, cs, cc) in enumerate(((x0, 0, c0), (x1, c0, c1))):
             if src is None or not ctx.needs_input_grad[i]:
+                continue
+            if pair is not None:
+                grads[i] = pair[i]
                 continue
             wp = ctx.wd[i]                       # packed in the forward (mnk_conv3x3_pack_all)
             # the source is the output of a norm layer (no pooling) and (presumably) has no other consumer: this launch also
             # leaves that layer's backward statistics (see _BN_OF); rows = the geometry both tensors share
-            rec = ctx.src_bn[i]
-            if rec is not None and (rec.c != cc or rec.y.shape[-1] != ceil4(cc) or small_bn(rec.y.numel() // rec.y.shape[-1], True, cc)
-                                    or _small_sync(rec.y.numel() // rec.y.shape[-1])):
-                rec = None               # (small layers make their backward statistics inside their own one-launch kernel)
+            rec = _dgrad_rec(ctx.src_bn[i], cc, None)
             res = None
             if ctx.up:
                 # data gradient w.r.t. the low-resolution source: one 4x4 / stride 2 convolution over dy (no gradient of
